@@ -36,10 +36,13 @@ failing check and ranks. Under the bench the kvx connector may not degrade a
 P/D pull to TCP (require_ipc): a failed IPC path is an error, never a silent
 1.6 GB msgpack per request.
 
-At N = 8 the P/D run is followed by BASELINE.json's literal split, 2P + 6D
-(``alt_split`` in the JSON; --alt-split none disables), and every result
-carries ``output_tok_s_per_gpu`` (whole job / N) next to the per-decode-GPU
-figure.
+A plain run sets up, warms up, times the K steps and prints the line. What
+takes runs of its own is behind ``--full``: on one GPU the fp8 child run
+(``fp8`` in the JSON), at N = 8 BASELINE.json's literal split, 2P + 6D, after
+the P/D run (``alt_split`` in the JSON; --alt-split 2p6d asks for it alone,
+--alt-split none disables). Every result carries ``output_tok_s_per_gpu``
+(whole job / N) next to the per-decode-GPU figure. ``--dump-outputs DIR``
+writes the tokens the last timed step returned, for build-to-build comparison.
 
 Output: one JSON line on rank 0 (see README "bench.py contract").
 """
@@ -127,9 +130,17 @@ def parse():
                    help="pd mode, routed: Poisson request rate of the open-loop phase (0 = 0.9 x closed-loop rate)")
     p.add_argument("--open-loop-requests", type=int, default=0)
     p.add_argument("--fp8-extra", default="auto", choices=["auto", "off"],
-                   help="agg mode, 1 GPU, bf16 run: also measure the reference AMD recipe's precision (W8A8 fp8 "
-                        "linears + fp8 KV) in a child process and report it under 'fp8' (the bf16 figure stays "
-                        "the value)")
+                   help="with --full, agg mode, 1 GPU, bf16 run: also measure the reference AMD recipe's precision "
+                        "(W8A8 fp8 linears + fp8 KV) in a child process and report it under 'fp8' (the bf16 figure "
+                        "stays the value)")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline run, also take the measurements that need runs of their own: the fp8 "
+                        "child run (--fp8-extra) on one GPU, the alternative P:D split (--alt-split auto) at N = 8")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="agg mode: write what the last timed step returned to its caller (one new token per request "
+                        "in flight) as DIR/<name>.npy, float64, rows ordered by request number; inputs are seeded, "
+                        "so two builds run with the same arguments can be compared output for output. Not "
+                        "implemented for --mode pd (the automatic mode from 8 GPUs on): the run exits with an error")
     return p.parse_args()
 
 
@@ -188,6 +199,8 @@ def main():
     if a.mode == "auto":
         a.mode = "pd" if world >= 8 else "agg"
     if a.mode == "pd":
+        if a.dump_outputs:
+            sys.exit("--dump-outputs covers the aggregated engine loop (--mode agg), not --mode pd")
         from llmd_amd.bench_pd import run_pd
 
         res = run_pd(a, rank, world, local_rank, log)
@@ -257,8 +270,16 @@ def main():
     def new_request(max_tokens):
         toks = rng.integers(100, vocab - 100, size=a.isl).tolist()
         nreq[0] += 1
-        eng.add_request(f"r{rank}-{nreq[0]}", toks,
-                        SamplingParams(max_tokens=max_tokens, temperature=0.0, ignore_eos=True))
+        return eng.add_request(f"r{rank}-{nreq[0]}", toks,
+                               SamplingParams(max_tokens=max_tokens, temperature=0.0, ignore_eos=True))
+
+    def setup_step():
+        added = 0
+        for o in eng.step():
+            if o.finished:
+                new_request(a.osl)
+                added += 1
+        return added
 
     # Setup (untimed, not part of warmup): admit C requests with staggered output
     # lengths, replacing each finished one at once (closed loop, as in the timed
@@ -266,20 +287,32 @@ def main():
     # prefill. Completions are then spread evenly over the next OSL steps, so
     # warmup/timed steps see steady-state serving (decodes + one new prefill per
     # OSL/C steps) instead of the initial all-prefill ramp or a refill burst.
-    for i in range(a.concurrency):
-        new_request(max(1, int(a.osl * (i + 1) / a.concurrency)))
+    # Only the first request's prompt is prefilled here. The other C - 1 start
+    # where a P/D decode engine starts a request (_land_prompt_kv): blocks of their
+    # own holding a copy of that prompt's KV, so the fill costs one prefill and
+    # C - 1 block copies, not C prefills (37 s of a 70B run whose timed steps
+    # take 3-7 s). Every prefill of the warmup and timed steps is computed.
     ts = time.time()
     setup_steps = 0
+    first = new_request(max(1, int(a.osl / a.concurrency)))
+    while first.num_computed_tokens < a.isl and not first.status.finished and setup_steps < 100000:
+        setup_step()
+        setup_steps += 1
+    landed = 0
+    _sync(a)  # the prefill's KV writes are done before they are read
+    for i in range(1, a.concurrency):
+        r = new_request(max(1, int(a.osl * (i + 1) / a.concurrency)))
+        landed += _land_prompt_kv(eng, r, first)
+    _sync(a)
+    if landed < a.concurrency - 1:
+        log(rank, f"warning: {a.concurrency - 1 - landed} of {a.concurrency - 1} prompts could not be landed as KV "
+                  f"copies and are prefilled in full: expect a long setup")
     t_note = ts
     # With C > OSL about one request completes per step, so a replacement always
     # waits at the check: then only this step's replacements may still wait.
     may_wait = a.concurrency > a.osl
     while setup_steps < 100000:
-        added = 0
-        for o in eng.step():
-            if o.finished:
-                new_request(a.osl)
-                added += 1
+        added = setup_step()
         setup_steps += 1
         if time.time() - t_note > 30:  # progress for long setups (silent runs read as hung)
             t_note = time.time()
@@ -296,17 +329,19 @@ def main():
     assert a.isl + longest <= max_len, (longest, max_len)
     _sync(a)
     log(rank, f"setup: {setup_steps} steps in {time.time() - ts:.1f}s (batch filled to {a.concurrency}, "
-              f"completions re-spaced to {a.concurrency}/{a.osl} per step)")
+              f"{landed} prompts landed as KV copies, completions re-spaced to {a.concurrency}/{a.osl} per step)")
 
     step_tokens = []
     step_ms = collections.defaultdict(list)  # step size -> wall ms (a step ends in a host sync on sampling)
 
     prev_n = [0]
+    last_outs = []  # what the latest step returned to its caller (--dump-outputs)
 
     def run_steps(n):
         for _ in range(n):
             ts0 = time.perf_counter()
-            for o in eng.step():
+            last_outs[:] = eng.step()
+            for o in last_outs:
                 if o.finished:
                     new_request(a.osl)
             # async scheduling: a call returns once the PREVIOUS step finished on the device
@@ -336,6 +371,8 @@ def main():
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t1
+    if a.dump_outputs:
+        _dump_outputs(a.dump_outputs, last_outs, rank, world)
     hist = collections.Counter(step_tokens)
     log(rank, "timed step sizes (tokens: steps, mean ms): " + ", ".join(
         f"{k}: {v} x {statistics.mean(step_ms[k]) if step_ms.get(k) else float('nan'):.1f}"
@@ -379,7 +416,7 @@ def main():
                    "parallelism": f"dp{world}" if a.mode == "agg" else f"pd{a.prefill_gpus}p{world - a.prefill_gpus}d",
                    "max_num_batched_tokens": a.max_num_batched_tokens, "block_size": a.block_size,
                    "graphs": not a.enforce_eager, "kv_cache_dtype": a.kv_cache_dtype,
-                   "async_scheduling": eng_async},
+                   "async_scheduling": eng_async, "setup_prompts_landed": landed},
         "output_tok_s_per_decode_gpu": round(value / max(1, n_decode_gpus), 2),
         "output_tok_s_per_gpu": round(value / world, 2),
         "p50_ttft_s": round(p50, 4) if p50 is not None else None,
@@ -388,7 +425,8 @@ def main():
         "steady_state": steady.window_report(n_prefills, a.steps * world, a.concurrency, a.osl),
         **_reference(a.model, value, world),
     }
-    if rank == 0 and world == 1 and a.device == "cuda" and a.quantization is None and a.fp8_extra == "auto":
+    if a.full and rank == 0 and world == 1 and a.device == "cuda" and a.quantization is None \
+            and a.fp8_extra == "auto":
         del eng
         import gc
 
@@ -405,6 +443,64 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def _land_prompt_kv(eng, r, src) -> bool:
+    """Start the waiting request ``r`` where a P/D decode engine starts one whose prompt a
+    prefill engine computed (engine/scheduler.py, step 0 of ``schedule``): fresh blocks for
+    the whole prompt, every prompt token but the last counted as computed, the last one run
+    by the next step for the first output token. The blocks are filled by a device copy of
+    ``src``'s prompt KV (a running request with a prompt as long and its prefill launched)
+    in place of a kvx pull: same bytes to read per decode step, no prefill FLOPs.
+    False - and ``r`` stays in the queue for a prefill of its own - when ``src`` is gone,
+    the pool has no room, or the engine's KV is not one rank's pool."""
+    sched, bm, runner = eng.sched, eng.bm, eng.runner
+    if runner.tp_size > 1 or eng.connector is not None or eng.offload is not None or not bm.has_seq(src.seq_id) \
+            or src.num_computed_tokens < r.num_prompt_tokens or len(sched.running) >= sched.sc.max_num_seqs:
+        return False
+    blocks = bm.allocate_remote(r.seq_id, r.num_prompt_tokens, r.cache_extra)
+    if not blocks:
+        return False
+    pairs = list(zip(blocks, bm.block_table(src.seq_id)))
+    _copy_blocks(runner.kv, pairs)
+    if runner.hybrid:  # windowed layers: 0 is the null block of a table's released head
+        swa = [(d, s) for d, s in zip(blocks.swa, bm.block_table_swa(src.seq_id)) if d]
+        _copy_blocks(runner.kv_swa, [(d, s) for d, s in swa if s])
+        # src keeps keys from isl - window + 1 on, a landed request's first query reaches one
+        # key further back: where that key opens a block, src has released it - zeros stand in
+        gone = [d for d, s in swa if not s]
+        if gone:
+            runner.kv_swa.view(torch.uint8).index_fill_(1, torch.tensor(gone, device=runner.kv_swa.device), 0)
+    sched.waiting.remove(r)
+    r.first_scheduled_time = time.monotonic()
+    sched.land_remote(r)
+    return True
+
+
+def _copy_blocks(pool, pairs):
+    """pool[:, dst] = pool[:, src] for (dst, src) block pairs of a [layers, blocks, ...] KV pool,
+    a layer at a time (the temporary stays at one layer's blocks), as raw bytes (fp8 pools)."""
+    if not pairs:
+        return
+    raw = pool.view({1: torch.uint8, 2: torch.int16, 4: torch.int32}[pool.element_size()])
+    dst = torch.tensor([d for d, _ in pairs], dtype=torch.long, device=pool.device)
+    src = torch.tensor([s for _, s in pairs], dtype=torch.long, device=pool.device)
+    for layer in raw:
+        layer.index_copy_(0, dst, layer.index_select(0, src))
+
+
+def _dump_outputs(out_dir, outs, rank, world):
+    """DIR/<name>.npy (float64): what the last timed step returned to its caller, one row per
+    request that got a token, ordered by request number. With async scheduling a call returns
+    the tokens of the step launched by the call before it."""
+    os.makedirs(out_dir, exist_ok=True)
+    rows = sorted((int(o.request_id.rsplit("-", 1)[1]), o) for o in outs if o.new_token_ids)
+    arrays = {"request_number": [n for n, _ in rows],
+              "token_ids": [o.new_token_ids[-1] for _, o in rows],
+              "num_output_tokens": [o.num_output_tokens for _, o in rows]}
+    sfx = f"_rank{rank}" if world > 1 else ""
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{sfx}.npy"), np.asarray(v, dtype=np.float64))
 
 
 def _fp8_extra(a) -> dict:
@@ -450,7 +546,7 @@ def _alt_split(a, rank, world, local_rank, log, main_res):
     steps; failures are reported in the JSON, never lost with the main result."""
     want = a.alt_split
     if want == "auto":
-        want = "2p6d" if world == 8 else "none"
+        want = "2p6d" if world == 8 and a.full else "none"
     if want in ("none", ""):
         return None
     try:

@@ -221,6 +221,16 @@ class Scheduler:
             return min(self.running, key=lambda r: (r.priority, -r.arrival_time))
         return self.running[-1]
 
+    def land_remote(self, r: Request):
+        """A request whose prompt KV was written into its ``allocate_remote`` blocks from
+        outside (a kvx pull; bench.py's setup) starts running: all prompt tokens but the
+        last are in the cache; the last one is recomputed locally to produce the first
+        output token's logits."""
+        r.num_computed_tokens = r.num_prompt_tokens - 1
+        r.num_cached_tokens = r.num_computed_tokens
+        r.status = Status.RUNNING
+        self.running.append(r)
+
     # ------------------------------------------------------------ schedule
     def schedule(self) -> SchedulerOutput:
         out = SchedulerOutput()
@@ -238,12 +248,7 @@ class Scheduler:
                     continue
                 ok = self.connector.recv_ok(rid)
                 if ok:
-                    # all prompt tokens but the last are in the cache; the last one is
-                    # recomputed locally to produce the first output token's logits
-                    r.num_computed_tokens = r.num_prompt_tokens - 1
-                    r.num_cached_tokens = r.num_computed_tokens
-                    r.status = Status.RUNNING
-                    self.running.append(r)
+                    self.land_remote(r)
                 else:
                     policy = (self.cfg.kv_transfer_config or {}).get("kv_load_failure_policy", "recompute")
                     if policy == "fail":

@@ -34,6 +34,29 @@ def pytest_collection_modifyitems(config, items):
             it.add_marker(skip)
 
 
+@pytest.fixture
+def uds_dir():
+    """A directory for Unix-socket files. sockaddr_un.sun_path holds 107 bytes, and
+    pytest's tmp_path under a deep TMPDIR plus the test's name is longer than that
+    (bind fails with "AF_UNIX path too long"), so sockets get a directory of their
+    own, 18 characters below the first temp root that leaves room for the file's
+    name, removed afterwards."""
+    import pathlib
+    import shutil
+    import tempfile
+
+    for base in (tempfile.gettempdir(), "/tmp", "/dev/shm"):
+        if len(base) <= 60 and os.path.isdir(base) and os.access(base, os.W_OK | os.X_OK):
+            d = tempfile.mkdtemp(prefix="llmd-uds-", dir=base)
+            break
+    else:
+        pytest.fail("no short writable directory for a Unix socket")
+    try:
+        yield pathlib.Path(d)
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+
+
 @pytest.fixture(autouse=True)
 def _seed_torch():
     """This PyTorch build seeds its default generator randomly per process, and

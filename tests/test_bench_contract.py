@@ -4,6 +4,7 @@ when more requests are in flight than output tokens (about one completion per
 step, so a replacement always waits at the setup check)."""
 import json
 import os
+import re
 import subprocess
 import sys
 
@@ -29,6 +30,39 @@ def test_bench_json_line_contract():
     assert d["steps"] == 6 and d["warmup"] == 2 and d["n_gpus"] == 1 and d["value"] > 0
     assert d["config"]["parallelism"] == "dp1" and d["dtype"] == "bf16"
     assert "timed step sizes" in err
+
+
+def test_bench_dump_outputs_repeat_run_for_run(tmp_path):
+    """--dump-outputs: the last timed step's tokens as float64 .npy files, rows by request
+    number; the seeded inputs make two runs with the same arguments agree value for value.
+    The setup lands all prompts but the first as KV copies; --full is accepted on any run."""
+    import numpy as np
+
+    args = ("--isl", "48", "--osl", "8", "--concurrency", "4", "--steps", "6", "--warmup", "2")
+    d1, err = _bench(*args, "--dump-outputs", str(tmp_path / "a"))
+    d2, _ = _bench(*args, "--full", "--dump-outputs", str(tmp_path / "b"))
+    assert "3 prompts landed as KV copies" in err and d1["config"]["setup_prompts_landed"] == 3
+    assert d1["steps"] == d2["steps"] == 6 and d1["ms_per_step"] > 0 and "fp8" not in d1
+    # --steps sets the number of timed steps: the per-size counts of the log line add up to it
+    sizes = re.search(r"timed step sizes \(tokens: steps, mean ms\): (.*)", err).group(1)
+    assert sum(int(m) for m in re.findall(r"\d+: (\d+) x", sizes)) == 6, sizes
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["num_output_tokens.npy", "request_number.npy", "token_ids.npy"]
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype == np.float64 and x.ndim == 1 and 0 < x.size <= 4
+        assert np.array_equal(x, y), (n, x, y)
+    num, tok, cnt = (np.load(tmp_path / "a" / f"{n}.npy") for n in ("request_number", "token_ids", "num_output_tokens"))
+    assert np.all(np.diff(num) > 0)
+    assert np.all((tok >= 0) & (tok < 512) & (tok == np.round(tok))), tok  # tiny-llama: 512 tokens
+    assert np.all((cnt >= 1) & (cnt <= 8)), cnt  # OSL 8
+    # it is the LAST step's output: one timed step fewer, and every request that got a token in
+    # both last steps had one output token less
+    _bench(*args[:-4], "--steps", "5", "--warmup", "2", "--dump-outputs", str(tmp_path / "c"))
+    num5, cnt5 = np.load(tmp_path / "c" / "request_number.npy"), np.load(tmp_path / "c" / "num_output_tokens.npy")
+    both = np.intersect1d(num, num5)
+    assert both.size > 0
+    assert np.array_equal(cnt[np.isin(num, both)], cnt5[np.isin(num5, both)] + 1), (num, cnt, num5, cnt5)
 
 
 def test_bench_setup_ends_with_more_in_flight_than_output_tokens():

@@ -457,16 +457,22 @@ import glob as _glob
 _GUIDES = sorted(_glob.glob("/root/reference/guides/*/router/*.values.yaml"))
 
 
-@pytest.mark.parametrize("values", _GUIDES or ["<reference tree not mounted>"],
-                         ids=[p.split("guides/")[1] for p in _GUIDES] or ["none"])
+@pytest.mark.parametrize("values", _GUIDES + [None],
+                         ids=[p.split("guides/")[1] for p in _GUIDES] + ["none"])
 def test_reference_guide_configs_route(values):
     """Every EndpointPickerConfig the reference's guides ship (plugin graphs
     verbatim from guides/*/router/*.values.yaml) loads and routes plain and
-    streamed completions over HTTP to role-labelled simulators."""
+    streamed completions over HTTP to role-labelled simulators. The case
+    ``none`` is collected with or without the reference tree, so the test's
+    ids do not depend on the machine: it skips where the tree is absent and
+    checks that the glob found the guides where it is mounted."""
     from llmd_amd.router.config import ConfigError, extract_config_text
 
     if not _GUIDES:
         pytest.skip("reference tree not mounted")
+    if values is None:
+        assert len(_GUIDES) >= 5, _GUIDES
+        return
     try:
         cfg = extract_config_text(open(values).read())
     except ConfigError:

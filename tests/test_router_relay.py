@@ -119,7 +119,7 @@ def _complete(buf: bytes) -> bool:
     return False
 
 
-def test_native_relay_contract(tmp_path):
+def test_native_relay_contract(uds_dir):
     async def main():
         engine, eport, seen = await _echo_engine()
         sims = [await start_sim(model="m", prefill_tps=1e6, decode_step_s=0.0005) for _ in range(3)]
@@ -135,7 +135,7 @@ def test_native_relay_contract(tmp_path):
             infos.append(dict(info))
             return orig(d, info)
         epp.on_response_complete = record
-        uds = str(tmp_path / "epp.sock")
+        uds = str(uds_dir / "epp.sock")
         srv = EppServer(epp)
         await srv.start(uds)
         port = _free_port()
@@ -258,7 +258,7 @@ def test_native_relay_contract(tmp_path):
             await srv.stop()
             relay.terminate()
             relay.wait(5)
-            relay2 = spawn(str(tmp_path / "nobody.sock"), "127.0.0.1", port, 1, "FailClose")
+            relay2 = spawn(str(uds_dir / "nobody.sock"), "127.0.0.1", port, 1, "FailClose")
             try:
                 await asyncio.sleep(0.3)
                 resp = await _raw(port, b"POST /v1/completions HTTP/1.1\r\nHost: x\r\nContent-Length: 2\r\n\r\n{}",
@@ -281,14 +281,14 @@ def test_native_relay_contract(tmp_path):
     asyncio.run(main())
 
 
-def test_native_relay_dead_endpoint_502(tmp_path):
+def test_native_relay_dead_endpoint_502(uds_dir):
     async def main():
         store = EndpointStore()
         epp = EPP(BASE, store, ControlPlane())
         dead = _free_port()
         await store.add(endpoints_from_yaml({"endpoints": [{"name": "d", "address": "127.0.0.1", "port": dead}]})[0])
         await epp.start()
-        uds = str(tmp_path / "epp.sock")
+        uds = str(uds_dir / "epp.sock")
         srv = EppServer(epp)
         await srv.start(uds)
         port = _free_port()
@@ -310,7 +310,7 @@ def test_native_relay_dead_endpoint_502(tmp_path):
     asyncio.run(main())
 
 
-def test_native_relay_bad_epp_frame_fails_over(tmp_path):
+def test_native_relay_bad_epp_frame_fails_over(uds_dir):
     """an EPP frame that does not decode must not leave its pick
     pending forever - the relay treats it as a lost EPP (FailClose -> 503)."""
     import struct
@@ -318,7 +318,7 @@ def test_native_relay_bad_epp_frame_fails_over(tmp_path):
     import msgpack
 
     async def main():
-        uds = str(tmp_path / "bad.sock")
+        uds = str(uds_dir / "bad.sock")
 
         async def serve(reader, writer):
             try:

@@ -30,7 +30,7 @@ from tests.test_router_e2e import BASE, _post, _serve
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_workers_share_one_epp(tmp_path):
+def test_workers_share_one_epp(uds_dir):
     async def main():
         sims = [await start_sim(model="m", prefill_tps=1e6, decode_step_s=0.0005) for _ in range(4)]
         eps = [{"name": f"s{i}", "address": "127.0.0.1", "port": p} for i, (_, _, p) in enumerate(sims)]
@@ -39,7 +39,7 @@ def test_workers_share_one_epp(tmp_path):
         for e in endpoints_from_yaml({"endpoints": eps}):
             await store.add(e)
         await epp.start()
-        uds = str(tmp_path / "epp.sock")
+        uds = str(uds_dir / "epp.sock")
         srv = EppServer(epp)
         await srv.start(uds)
         fronts = []
