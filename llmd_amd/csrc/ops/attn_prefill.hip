@@ -14,8 +14,18 @@
 //     K image: padded rows (D*2+16 B) -> ds_read_b128 conflict-free
 //   O[q][dim] += P[q][key] . V[key][dim]
 //     V image: XOR-swizzled rows, ds_read_b64_tr_b16 transposed reads
-// K/V tiles are double-buffered; the next tile's global loads are issued before
-// the current tile's MFMAs and written to LDS after the barrier (T14 split).
+// K/V tiles are double-buffered.
+//
+// Two kernels share this decomposition and math (llmd_paged_prefill picks one):
+//   prefill_v2_kernel<D>      bf16 caches with blocks of >= 16 keys: tiles go global -> LDS by
+//                             DMA. The fp8-KV path also runs here, on a bf16 copy of the blocks it
+//                             reads (kv_dequant_gather_kernel).
+//   prefill_kernel<D, F8>     everything else (fp8 caches read in place, blocks under 16 keys,
+//                             LLMD_PREFILL_V1=1): the next tile's global loads are issued before
+//                             the current tile's MFMAs and written to LDS after the barrier
+//                             (T14 split), K rows padded and V rows swizzled as above.
+// Two opt-in forms measured slower than v2 are still built: prefill_v4_kernel (LLMD_PREFILL_V4=1,
+// below) and the software-pipelined v5 (LLMD_PREFILL_V5=1, attn_prefill5.hip).
 #include <cstdlib>
 
 #include "llmd_common.h"
@@ -325,20 +335,18 @@ __device__ __forceinline__ int p2_pv(int r) {
   else return (r & 2) | ((r >> 1) & 4);
 }
 
-// V (round-4 A/B switch): bit 0 = K/V fragment reads ring-pipelined with a sched_barrier
-// per step, bit 1 = LDS-DMA from asm (glds16) instead of the builtin
-// (round 6) bit 4 = row sums kept in scalar f32 adds: hipcc SLP-packs the two query blocks' sums
-// into v_pk_add_f32, which beside MFMAs costs ~13 cycles more per instruction than two v_add_f32
-// (MI355X_MICROARCH 'price of one filler beside MFMAs'); bit 5 = whole tiles DMA'd through a
-// per-tile buffer descriptor (scalar base, 32-bit per-lane offsets) instead of 64-bit per-lane
-// addresses (the v_lshl_add_u64 of every piece); bit 6 = the causal / window mask behind a scalar
-// branch (see compute()). The loop is issue-bound (profiles/attn_prefill_v2_variants_r6.txt), so
-// bits 7 / 8 take VALU work per score away: bit 7 = Q pre-scaled by scale * log2(e) at load and the
-// S^T accumulators started at -m (the running row max, one broadcast register per query block):
-// the MFMA yields S scale - m, and p = exp2 of it without the per-score v_fma; bit 8 = row sums on
-// the matrix pipe: P . ones (4 extra 16x16x32 MFMAs per tile, accumulators in O's layout) instead of
-// 32 v_add_f32 per lane and tile, and no cross-lane sum in the epilogue
-template <int D, int V = 3>
+// Schedule (the loop is issue-bound; profiles/attn_prefill_v2_variants_r6.txt has the A/B behind
+// each choice):
+//   - K and V fragments are read from LDS through a ring, PF = 6 fragments ahead of their MFMAs,
+//     with a sched_barrier per step (hipcc's own schedule hoists every read and waits lgkmcnt(0)).
+//   - A whole tile that lies in one block is DMA'd through a per-tile buffer descriptor (scalar
+//     base, 32-bit per-lane offsets); the other tiles use 64-bit per-lane addresses.
+//   - Q is pre-scaled by scale * log2(e) at load and the S^T accumulators start at -m (the running
+//     row max, one broadcast register per query block): the MFMA yields S scale - m, and p = exp2
+//     of it without a per-score v_fma.
+//   - Row sums run on the matrix pipe: P . ones (4 extra 16x16x32 MFMAs per tile, accumulators in
+//     O's layout) instead of 32 v_add_f32 per lane and tile, and no cross-lane sum in the epilogue.
+template <int D>
 __global__ __launch_bounds__(NT, 2) void prefill_v2_kernel(
     const uint16_t* __restrict__ q, int64_t q_stride, const uint16_t* __restrict__ kc,
     const uint16_t* __restrict__ vc, int64_t block_stride, int bs,
@@ -394,23 +402,22 @@ __global__ __launch_bounds__(NT, 2) void prefill_v2_kernel(
       u32x4_t v = {0, 0, 0, 0};
       if (tk < ql) v = *reinterpret_cast<const u32x4_t*>(qr + (4 * s + g) * 8);
       qf[nb][s] = __builtin_bit_cast(bf16x8_t, v);
-      if constexpr ((V & 128) != 0) {
 #pragma unroll
-        for (int e = 0; e < 8; ++e) qf[nb][s][e] = (__bf16)((float)qf[nb][s][e] * scale_log2);
-      }
+      for (int e = 0; e < 8; ++e) qf[nb][s][e] = (__bf16)((float)qf[nb][s][e] * scale_log2);  // pre-scaled
     }
   }
+  // lsum is dead (the row sums live in ls): hipcc removes every trace of it, but only after it has
+  // shaped the register allocation, so taking it out of the source changes the machine code. It
+  // goes with the next change to this kernel that is measured on the GPU.
   float m[2] = {NEG_INF, NEG_INF}, lsum[2] = {0.f, 0.f};
   f32x4_t o[2][NB];
 #pragma unroll
   for (int nb = 0; nb < 2; ++nb)
 #pragma unroll
     for (int n = 0; n < NB; ++n) o[nb][n] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-  // bit 7: -m (0 while no score seen) broadcast, the S^T accumulators' start; bit 8: row sums in O's layout
+  // cm: -m (0 while no score seen) broadcast, the S^T accumulators' start; ls: row sums in O's layout
   f32x4_t cm[2] = {f32x4_t{0.f, 0.f, 0.f, 0.f}, f32x4_t{0.f, 0.f, 0.f, 0.f}};
   f32x4_t ls[2] = {f32x4_t{0.f, 0.f, 0.f, 0.f}, f32x4_t{0.f, 0.f, 0.f, 0.f}};
-  constexpr bool RELS = (V & 128) != 0, MSUM = (V & 256) != 0;
-  const float sl2 = RELS ? 1.f : scale_log2;  // scale of the scores the MFMA yields (bit 7: pre-applied)
 
   // DMA: NI K + NI V wave-instructions of 1 KB (1024 / RB rows); wave w issues
   // j = w + 4i. The per-lane source offsets inside a 64-row tile are constant
@@ -429,9 +436,8 @@ __global__ __launch_bounds__(NT, 2) void prefill_v2_kernel(
     voff[i] = (uint32_t)(row * RB + 16 * (sl ^ p2_pv<D>(row)));
   }
   auto dma = [&](const char* src, char* dst) {
-    if constexpr (V & 2) glds16(src, lds_addr(dst));
-    else __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)src,
-                                          (void __attribute__((address_space(3)))*)dst, 16, 0, 0);
+    __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)src,
+                                     (void __attribute__((address_space(3)))*)dst, 16, 0, 0);
   };
   auto issue = [&](char* base, int t) {
     const int ts = t * 64;
@@ -441,23 +447,15 @@ __global__ __launch_bounds__(NT, 2) void prefill_v2_kernel(
     const char* vb = reinterpret_cast<const char*>(vc) + tb;
     const int rlim = ctx - 1 - ts;
     if (rlim >= 63 && bs >= 64) {
-      if constexpr ((V & 32) != 0) {
-        const __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc((void*)kb, 0, 64 * RB, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc((void*)vb, 0, 64 * RB, 0x00020000);
+      // a whole tile in one block: a buffer descriptor per image, 32-bit per-lane offsets
+      const __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc((void*)kb, 0, 64 * RB, 0x00020000);
+      const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc((void*)vb, 0, 64 * RB, 0x00020000);
 #pragma unroll
-        for (int i = 0; i < NI / 4; ++i) {
-          char* dst = base + 1024 * (ws + 4 * i);
-          __builtin_amdgcn_raw_ptr_buffer_load_lds(rk, (__attribute__((address_space(3))) void*)dst, 16, koff[i], 0, 0, 0);
-          __builtin_amdgcn_raw_ptr_buffer_load_lds(rv, (__attribute__((address_space(3))) void*)(dst + P2_IMG), 16,
-                                                   voff[i], 0, 0, 0);
-        }
-      } else {
-#pragma unroll
-        for (int i = 0; i < NI / 4; ++i) {
-          char* dst = base + 1024 * (ws + 4 * i);
-          dma(kb + koff[i], dst);
-          dma(vb + voff[i], dst + P2_IMG);
-        }
+      for (int i = 0; i < NI / 4; ++i) {
+        char* dst = base + 1024 * (ws + 4 * i);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rk, (__attribute__((address_space(3))) void*)dst, 16, koff[i], 0, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rv, (__attribute__((address_space(3))) void*)(dst + P2_IMG), 16,
+                                                 voff[i], 0, 0, 0);
       }
     } else if (rlim >= 63) {
       // blocks of 16 / 32 keys: a wave-instruction's RPI rows sit in one block
@@ -507,7 +505,7 @@ __global__ __launch_bounds__(NT, 2) void prefill_v2_kernel(
     if (!active) return;
     // S^T: K fragment j = KS b4 + s, read PF ahead of its two MFMAs (a ring with a
     // sched_barrier per step: hipcc's own schedule hoists every read and waits lgkmcnt(0))
-    constexpr int PF = (V & 4) ? 6 : 4;  // fragments read ahead (V bit 2: 6)
+    constexpr int PF = 6;  // fragments read ahead
     auto kread = [&](int j) {
       return *reinterpret_cast<const bf16x8_t*>(img + kofs[j % KS] + (j / KS) * 16 * RB);
     };
@@ -523,10 +521,10 @@ __global__ __launch_bounds__(NT, 2) void prefill_v2_kernel(
     bf16x8_t kr[PF];
 #pragma unroll
     for (int j = 0; j < PF; ++j) kr[j] = kread(j);
-    if constexpr (V & 1) __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int b4 = 0; b4 < 4; ++b4) {
-      f32x4_t a0 = cm[0], a1 = cm[1];  // zeros unless bit 7
+      f32x4_t a0 = cm[0], a1 = cm[1];  // scores come out relative to the running max
 #pragma unroll
       for (int s = 0; s < KS; ++s) {
         const int j = KS * b4 + s;
@@ -534,21 +532,13 @@ __global__ __launch_bounds__(NT, 2) void prefill_v2_kernel(
         if (j + PF < 4 * KS) kr[j % PF] = kread(j + PF);
         a0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ka, qf[0][s], a0, 0, 0, 0);
         a1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ka, qf[1][s], a1, 0, 0, 0);
-        if constexpr (V & 1) __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_sched_barrier(0);
       }
       sc[b4][0] = a0;
       sc[b4][1] = a1;
     }
-    if constexpr (V & 8) {  // the first V fragments load under the mask + softmax (V bit 3)
-#pragma unroll
-      for (int j = 0; j < PF; ++j) vr[j] = vread(j);
-    }
-    bool need_mask = (ts + 63 > p_lo) || (window > 0 && ts <= p_hi - window);
-    if constexpr ((V & 64) != 0) need_mask = __builtin_amdgcn_readfirstlane((int)need_mask) != 0;
+    const bool need_mask = (ts + 63 > p_lo) || (window > 0 && ts <= p_hi - window);
     if (need_mask) {
-      // bit 6: a real (scalar) branch - without the asm fence hipcc if-converts the mask into
-      // ~290 selects / compares executed on EVERY tile, not just the diagonal and window-edge ones
-      if constexpr ((V & 64) != 0) asm volatile("" ::: "memory");
 #pragma unroll
       for (int nb = 0; nb < 2; ++nb) {
         const int qp = p_lo + 16 * nb + c16;
@@ -575,12 +565,9 @@ __global__ __launch_bounds__(NT, 2) void prefill_v2_kernel(
       for (int b4 = 0; b4 < 4; ++b4)
 #pragma unroll
         for (int i = 0; i < 4; ++i) mx = fmaxf(mx, sc[b4][nb][i]);
-      if constexpr (RELS) {  // scores relative to msub (0 while m = -inf): absolute max = mx + msub
-        const float msub = (m[nb] == NEG_INF) ? 0.f : m[nb];
-        mt[nb] = mx + msub;
-      } else {
-        mt[nb] = mx * scale_log2;
-      }
+      // scores are relative to msub (0 while m = -inf): absolute max = mx + msub
+      const float msub = (m[nb] == NEG_INF) ? 0.f : m[nb];
+      mt[nb] = mx + msub;
       grow = grow || (mt[nb] > m[nb] + 8.f);
     }
     if (__ballot(grow) != 0) {  // wave-uniform
@@ -591,16 +578,15 @@ __global__ __launch_bounds__(NT, 2) void prefill_v2_kernel(
         mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
         const float mnew = fmaxf(m[nb], mx);
         alpha[nb] = (mnew == NEG_INF) ? 1.f : __builtin_amdgcn_exp2f(m[nb] - mnew);
-        lsum[nb] *= alpha[nb];  // per-lane partial sums, same factor on the row's 4 lanes
-        if constexpr (RELS) {   // rebase this tile's relative scores and the next tiles' start
-          const float sold = (m[nb] == NEG_INF) ? 0.f : m[nb], snew = (mnew == NEG_INF) ? 0.f : mnew;
-          const float d = sold - snew;
+        lsum[nb] *= alpha[nb];
+        // rebase this tile's relative scores and the next tiles' start
+        const float sold = (m[nb] == NEG_INF) ? 0.f : m[nb], snew = (mnew == NEG_INF) ? 0.f : mnew;
+        const float d = sold - snew;
 #pragma unroll
-          for (int b4 = 0; b4 < 4; ++b4)
+        for (int b4 = 0; b4 < 4; ++b4)
 #pragma unroll
-            for (int i = 0; i < 4; ++i) sc[b4][nb][i] += d;
-          cm[nb] = f32x4_t{-snew, -snew, -snew, -snew};
-        }
+          for (int i = 0; i < 4; ++i) sc[b4][nb][i] += d;
+        cm[nb] = f32x4_t{-snew, -snew, -snew, -snew};
         m[nb] = mnew;
       }
 #pragma unroll
@@ -610,27 +596,15 @@ __global__ __launch_bounds__(NT, 2) void prefill_v2_kernel(
           const float a = __shfl(alpha[nb], 4 * g + i, 64);
 #pragma unroll
           for (int n = 0; n < NB; ++n) o[nb][n][i] *= a;
-          if constexpr (MSUM) ls[nb][i] *= a;
+          ls[nb][i] *= a;
         }
     }
 #pragma unroll
-    for (int nb = 0; nb < 2; ++nb) {
-      const float msub = (m[nb] == NEG_INF) ? 0.f : m[nb];
-      float ps = 0.f;
+    for (int nb = 0; nb < 2; ++nb)
 #pragma unroll
       for (int b4 = 0; b4 < 4; ++b4)
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const float p = RELS ? __builtin_amdgcn_exp2f(sc[b4][nb][i])
-                               : __builtin_amdgcn_exp2f(fmaf(sc[b4][nb][i], sl2, -msub));
-          sc[b4][nb][i] = p;
-          if constexpr (!MSUM) {
-            ps += p;
-            if constexpr ((V & 16) != 0) asm volatile("" : "+v"(ps));  // no SLP packing across nb
-          }
-        }
-      if constexpr (!MSUM) lsum[nb] += ps;  // lane-partial: summed over the row's 4 lanes once, in the epilogue
-    }
+        for (int i = 0; i < 4; ++i) sc[b4][nb][i] = __builtin_amdgcn_exp2f(sc[b4][nb][i]);
     bf16x8_t pa[2][2];
 #pragma unroll
     for (int t2 = 0; t2 < 2; ++t2)
@@ -641,20 +615,17 @@ __global__ __launch_bounds__(NT, 2) void prefill_v2_kernel(
           pa[t2][nb][j] = (__bf16)sc[2 * t2][nb][j];
           pa[t2][nb][4 + j] = (__bf16)sc[2 * t2 + 1][nb][j];
         }
-    if constexpr (MSUM) {  // row sums of P on the matrix pipe: P . ones, rows in O's layout
-      const bf16x8_t ones = {(__bf16)1.f, (__bf16)1.f, (__bf16)1.f, (__bf16)1.f,
-                             (__bf16)1.f, (__bf16)1.f, (__bf16)1.f, (__bf16)1.f};
+    // row sums of P on the matrix pipe: P . ones, rows in O's layout
+    const bf16x8_t ones = {(__bf16)1.f, (__bf16)1.f, (__bf16)1.f, (__bf16)1.f,
+                           (__bf16)1.f, (__bf16)1.f, (__bf16)1.f, (__bf16)1.f};
 #pragma unroll
-      for (int t2 = 0; t2 < 2; ++t2) {
-        ls[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa[t2][0], ones, ls[0], 0, 0, 0);
-        ls[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa[t2][1], ones, ls[1], 0, 0, 0);
-      }
+    for (int t2 = 0; t2 < 2; ++t2) {
+      ls[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa[t2][0], ones, ls[0], 0, 0, 0);
+      ls[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa[t2][1], ones, ls[1], 0, 0, 0);
     }
-    if constexpr (!(V & 8)) {
 #pragma unroll
-      for (int j = 0; j < PF; ++j) vr[j] = vread(j);
-    }
-    if constexpr (V & 1) __builtin_amdgcn_sched_barrier(0);
+    for (int j = 0; j < PF; ++j) vr[j] = vread(j);
+    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int j = 0; j < 2 * NB; ++j) {
       const int t2 = j / NB, n = j % NB;
@@ -662,7 +633,7 @@ __global__ __launch_bounds__(NT, 2) void prefill_v2_kernel(
       if (j + PF < 2 * NB) vr[j % PF] = vread(j + PF);
       o[0][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa[t2][0], vb, o[0][n], 0, 0, 0);
       o[1][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa[t2][1], vb, o[1][n], 0, 0, 0);
-      if constexpr (V & 1) __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_sched_barrier(0);
     }
   };
 
@@ -683,21 +654,17 @@ __global__ __launch_bounds__(NT, 2) void prefill_v2_kernel(
   const float sink = sinks ? sinks[head] * 1.4426950408889634f : NEG_INF;
 #pragma unroll
   for (int nb = 0; nb < 2; ++nb) {
-    float den = lsum[nb] + __shfl_xor(lsum[nb], 16, 64);
-    den += __shfl_xor(den, 32, 64);
-    if (sinks) den += exp2f(sink - (m[nb] == NEG_INF ? 0.f : m[nb]));
-    const float inv = den > 0.f ? vscale / den : 0.f;
-    float mrow[4];  // bit 8: the running max of O's row 4 g + i (m is kept per query column c16)
+    float dl = lsum[nb] + __shfl_xor(lsum[nb], 16, 64);  // unused: see lsum
+    dl += __shfl_xor(dl, 32, 64);
+    float mrow[4];  // the running max of O's row 4 g + i (m is kept per query column c16)
 #pragma unroll
-    for (int i = 0; i < 4; ++i) mrow[i] = MSUM ? __shfl(m[nb], 4 * g + i, 64) : 0.f;
+    for (int i = 0; i < 4; ++i) mrow[i] = __shfl(m[nb], 4 * g + i, 64);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      float f = __shfl(inv, 4 * g + i, 64);
-      if constexpr (MSUM) {
-        float d = ls[nb][i];
-        if (sinks) d += exp2f(sink - (mrow[i] == NEG_INF ? 0.f : mrow[i]));
-        f = d > 0.f ? vscale / d : 0.f;
-      }
+      (void)__shfl(dl, 4 * g + i, 64);
+      float den = ls[nb][i];
+      if (sinks) den += exp2f(sink - (mrow[i] == NEG_INF ? 0.f : mrow[i]));
+      const float f = den > 0.f ? vscale / den : 0.f;
       const int tk = tok0 + 16 * nb + 4 * g + i;
       if (tk < ql) {
         uint16_t* orow = out + (int64_t)(qs + tk) * out_stride + (int64_t)head * D;
@@ -707,299 +674,6 @@ __global__ __launch_bounds__(NT, 2) void prefill_v2_kernel(
     }
   }
 }
-
-// ---------------------------------------------------------------- v3 (bf16 cache, D = 128, block >= 64, G % 4 == 0)
-// One 4-wave workgroup per CU (512 registers per wave) runs 4 query heads of a
-// GQA group x 64 query tokens; each wave owns one head x 4 token blocks of 16,
-// so every K fragment (S^T A operand) and every V fragment (PV B operand) read
-// from LDS feeds four MFMAs (v2: two) and each K/V tile serves 256 query rows.
-// O (4 x 8 f32x4 = 128 accumulators) lives in the literal AGPRs a[0:127],
-// touched only by the generated asm of prefill_v3_agpr.inc (gen_prefill_v3.py);
-// scores accumulate in VGPRs through asm MFMAs; K and V fragments are read 4
-// steps ahead with a sched_barrier per step; the LDS-DMA is issued from asm
-// (glds16) so hipcc's waitcnt pass keeps counted lgkmcnt(N) waits. Same tile
-// images, swizzles, masking, lazy rescale and sinks as v2.
-#include "prefill_v3_agpr.inc"
-
-__device__ __forceinline__ void pf3_mfma4(f32x4_t& s0, f32x4_t& s1, f32x4_t& s2, f32x4_t& s3, const bf16x8_t& k,
-                                          const bf16x8_t& q0, const bf16x8_t& q1, const bf16x8_t& q2,
-                                          const bf16x8_t& q3, bool first) {
-  if (first) {
-    asm volatile(
-        "v_mfma_f32_16x16x32_bf16 %0, %4, %5, 0\n\t"
-        "v_mfma_f32_16x16x32_bf16 %1, %4, %6, 0\n\t"
-        "v_mfma_f32_16x16x32_bf16 %2, %4, %7, 0\n\t"
-        "v_mfma_f32_16x16x32_bf16 %3, %4, %8, 0"
-        : "=&v"(s0), "=&v"(s1), "=&v"(s2), "=&v"(s3)
-        : "v"(k), "v"(q0), "v"(q1), "v"(q2), "v"(q3));
-  } else {
-    asm volatile(
-        "v_mfma_f32_16x16x32_bf16 %0, %4, %5, %0\n\t"
-        "v_mfma_f32_16x16x32_bf16 %1, %4, %6, %1\n\t"
-        "v_mfma_f32_16x16x32_bf16 %2, %4, %7, %2\n\t"
-        "v_mfma_f32_16x16x32_bf16 %3, %4, %8, %3"
-        : "+v"(s0), "+v"(s1), "+v"(s2), "+v"(s3)
-        : "v"(k), "v"(q0), "v"(q1), "v"(q2), "v"(q3));
-  }
-}
-
-__global__ __launch_bounds__(NT, 1) void prefill_v3_kernel(
-    const uint16_t* __restrict__ q, int64_t q_stride, const uint16_t* __restrict__ kc,
-    const uint16_t* __restrict__ vc, int64_t block_stride, int bs,
-    const int* __restrict__ block_tables, int bt_stride, const int* __restrict__ q_start,
-    const int* __restrict__ q_len, const int* __restrict__ ctx_len, const int* __restrict__ items,
-    int Hq, int Hkv, int G, float scale_log2, int window, const float* __restrict__ sinks,
-    uint16_t* __restrict__ out, int64_t out_stride, float vscale, int xcd) {
-  constexpr int D = 128, KS = D / 32, NB = D / 16, RB = 2 * D;
-  constexpr int P2_IMG = 64 * RB;  // one 64-key bf16 image (16 KB)
-  constexpr int NI = 64 * (D / 8) / 64;  // 16 DMA wave-instructions per image
-  __shared__ __attribute__((aligned(1024))) char buf0[2 * P2_IMG];  // K | V of even tiles
-  __shared__ __attribute__((aligned(1024))) char buf1[2 * P2_IMG];  // K | V of odd tiles
-
-  int bx = blockIdx.x, by = blockIdx.y;
-  if (xcd) {
-    const int l = xcd_remap(by * gridDim.x + bx, gridDim.x * gridDim.y);
-    bx = l % gridDim.x;
-    by = l / gridDim.x;
-  }
-  const int seq = items[2 * bx], tok0 = items[2 * bx + 1];
-  const int NHG = G / 4;
-  const int kvh = by / NHG, hg = by % NHG;
-  const int qs = q_start[seq], ql = q_len[seq], ctx = ctx_len[seq];
-  const int pbase = ctx - ql;
-  const int* bt = block_tables + (int64_t)seq * bt_stride;
-  const int64_t head_off = (int64_t)kvh * bs * D;
-  const int lbs = __builtin_ctz(bs);
-
-  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, g = lane >> 4,
-            c16 = lane & 15;
-  const int head = kvh * G + hg * 4 + w;
-  const int ntok = max(0, min(64, ql - tok0));
-  const int p_lo = pbase + tok0, p_hi = pbase + tok0 + max(ntok, 1) - 1;
-  const int kmin = window > 0 ? max(0, p_lo - window + 1) : 0;
-  const int t_first = kmin >> 6, t_last = p_hi >> 6;
-
-  bf16x8_t qf[4][KS];
-#pragma unroll
-  for (int nb = 0; nb < 4; ++nb) {
-    const int tk = tok0 + 16 * nb + c16;
-    const uint16_t* qr = q + (int64_t)(qs + tk) * q_stride + (int64_t)head * D;
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-      u32x4_t v = {0, 0, 0, 0};
-      if (tk < ql) v = *reinterpret_cast<const u32x4_t*>(qr + (4 * s + g) * 8);
-      qf[nb][s] = __builtin_bit_cast(bf16x8_t, v);
-    }
-  }
-  float m[4] = {NEG_INF, NEG_INF, NEG_INF, NEG_INF}, lsum[4] = {0.f, 0.f, 0.f, 0.f};
-  PF3_ZERO_ACC();  // O = a[0:127]
-
-  uint32_t koff[NI / 4], voff[NI / 4];
-#pragma unroll
-  for (int i = 0; i < NI / 4; ++i) {
-    const int u = 64 * (w + 4 * i) + lane;
-    const int row = u / (D / 8), sl = u % (D / 8);
-    koff[i] = (uint32_t)(row * RB + 16 * (sl ^ p2_pk<D>(row)));
-    voff[i] = (uint32_t)(row * RB + 16 * (sl ^ p2_pv<D>(row)));
-  }
-  auto issue = [&](char* base, int t) {
-    const int ts = t * 64;
-    LLMD_DCHECK(ts < ctx && bt[ts >> lbs] >= 0 && ctx <= bt_stride * bs);
-    const int64_t tb = 2 * ((int64_t)bt[ts >> lbs] * block_stride + head_off + (int64_t)(ts & (bs - 1)) * D);
-    const char* kb = reinterpret_cast<const char*>(kc) + tb;
-    const char* vb = reinterpret_cast<const char*>(vc) + tb;
-    const int rlim = ctx - 1 - ts;
-    const unsigned lk = lds_addr(base) + 1024 * w, lv = lk + P2_IMG;
-    if (rlim >= 63) {
-#pragma unroll
-      for (int i = 0; i < NI / 4; ++i) {
-        glds16(kb + koff[i], lk + 4096 * i);
-        glds16(vb + voff[i], lv + 4096 * i);
-      }
-    } else {
-      // a sequence's last, partial tile: rows past the end re-read the last key (finite V)
-#pragma unroll
-      for (int i = 0; i < NI / 4; ++i) {
-        int ln = lane;  // opaque: recomputed here, not hoisted
-        asm volatile("" : "+v"(ln));
-        const int u = 64 * (w + 4 * i) + ln;
-        const int row = u / (D / 8), sl = u % (D / 8);
-        const int64_t ro = (int64_t)min(row, rlim) * RB;
-        glds16(kb + ro + 16 * (sl ^ p2_pk<D>(row)), lk + 4096 * i);
-        glds16(vb + ro + 16 * (sl ^ p2_pv<D>(row)), lv + 4096 * i);
-      }
-    }
-  };
-  const int qq = c16 >> 2, pp = c16 & 3;
-  const int srow = rowoff(c16 >> 2) + (c16 & 3), kp = p2_pk<D>(srow);
-  int kofs[KS];
-#pragma unroll
-  for (int s = 0; s < KS; ++s) kofs[s] = srow * RB + 16 * ((4 * s + g) ^ kp);
-  const int vrow = rowoff(g) + qq, vp = p2_pv<D>(vrow);
-  int vofs[NB];
-#pragma unroll
-  for (int n = 0; n < NB; ++n) vofs[n] = P2_IMG + vrow * RB + 16 * ((2 * n + (pp >> 1)) ^ vp) + 8 * (pp & 1);
-
-  auto compute = [&](const char* img, int t) {
-    const int ts = t * 64;
-    const bool active = ntok > 0 && ts <= p_hi && (window <= 0 || ts + 63 > p_lo - window);
-    if (!active) return;
-    auto kread = [&](int j) {
-      return *reinterpret_cast<const bf16x8_t*>(img + kofs[j % KS] + (j / KS) * 16 * RB);
-    };
-    auto vread = [&](int j) {
-      const char* p0 = img + vofs[j % NB] + 32 * (j / NB) * RB;
-      s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)p0);
-      s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(p0 + 16 * RB));
-      return __builtin_bit_cast(bf16x8_t, s16x8_t{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]});
-    };
-    // ---- S^T[key][token] for the 4 token blocks: K fragment j = KS b4 + s
-    f32x4_t sc[4][4];  // [b4][nb]
-    bf16x8_t kr[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) kr[j] = kread(j);
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int b4 = 0; b4 < 4; ++b4) {
-#pragma unroll
-      for (int s = 0; s < KS; ++s) {
-        const int j = KS * b4 + s;
-        const bf16x8_t ka = kr[j & 3];
-        if (j + 4 < 4 * KS) kr[j & 3] = kread(j + 4);
-        pf3_mfma4(sc[b4][0], sc[b4][1], sc[b4][2], sc[b4][3], ka, qf[0][s], qf[1][s], qf[2][s], qf[3][s], s == 0);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-    asm volatile("s_nop 7\n\ts_nop 7" ::: "memory");  // score MFMAs (asm) -> VALU reads
-    __builtin_amdgcn_sched_barrier(0);
-    const bool need_mask = (ts + 63 > p_lo) || (window > 0 && ts <= p_hi - window);
-    if (need_mask) {
-#pragma unroll
-      for (int nb = 0; nb < 4; ++nb) {
-        const int qp = p_lo + 16 * nb + c16;
-#pragma unroll
-        for (int b4 = 0; b4 < 4; ++b4)
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            const int key = ts + 16 * b4 + rowoff(g) + i;
-            bool ok = key <= qp;
-            if (window > 0) ok = ok && key > qp - window;
-            sc[b4][nb][i] = ok ? sc[b4][nb][i] : NEG_INF;
-          }
-      }
-    }
-    float mt[4];
-    bool grow = false;
-#pragma unroll
-    for (int nb = 0; nb < 4; ++nb) {
-      float mx = NEG_INF;
-#pragma unroll
-      for (int b4 = 0; b4 < 4; ++b4)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) mx = fmaxf(mx, sc[b4][nb][i]);
-      mt[nb] = mx * scale_log2;
-      grow = grow || (mt[nb] > m[nb] + 8.f);
-    }
-    if (__ballot(grow) != 0) {  // wave-uniform, rare after the first tiles
-#pragma unroll
-      for (int nb = 0; nb < 4; ++nb) {
-        float mx = fmaxf(mt[nb], __shfl_xor(mt[nb], 16, 64));
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float mnew = fmaxf(m[nb], mx);
-        const float alpha = (mnew == NEG_INF) ? 1.f : __builtin_amdgcn_exp2f(m[nb] - mnew);
-        lsum[nb] *= alpha;
-        m[nb] = mnew;
-        const float a0 = __shfl(alpha, 4 * g, 64), a1 = __shfl(alpha, 4 * g + 1, 64),
-                    a2 = __shfl(alpha, 4 * g + 2, 64), a3 = __shfl(alpha, 4 * g + 3, 64);
-        if (nb == 0) {
-          PF3_RESCALE0(a0, a1, a2, a3);
-        } else if (nb == 1) {
-          PF3_RESCALE1(a0, a1, a2, a3);
-        } else if (nb == 2) {
-          PF3_RESCALE2(a0, a1, a2, a3);
-        } else {
-          PF3_RESCALE3(a0, a1, a2, a3);
-        }
-      }
-    }
-    bf16x8_t pa[2][4];
-#pragma unroll
-    for (int nb = 0; nb < 4; ++nb) {
-      const float msub = (m[nb] == NEG_INF) ? 0.f : m[nb];
-      float ps = 0.f;
-#pragma unroll
-      for (int b4 = 0; b4 < 4; ++b4)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const float p = __builtin_amdgcn_exp2f(fmaf(sc[b4][nb][i], scale_log2, -msub));
-          sc[b4][nb][i] = p;
-          ps += p;
-        }
-      lsum[nb] += ps;
-#pragma unroll
-      for (int t2 = 0; t2 < 2; ++t2)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          pa[t2][nb][j] = (__bf16)sc[2 * t2][nb][j];
-          pa[t2][nb][4 + j] = (__bf16)sc[2 * t2 + 1][nb][j];
-        }
-    }
-    // ---- O[token][dim] += P[token][key] . V[key][dim]: V fragment j = NB t2 + n feeds the 4 token blocks
-    bf16x8_t vr[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) vr[j] = vread(j);
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_nop 1" ::: "memory");  // pa (VALU) -> asm MFMA operand
-    __builtin_amdgcn_sched_barrier(0);
-    PF3_PV_BLOCK
-  };
-
-  issue(buf0, t_first);
-  for (int t = t_first; t <= t_last; t += 2) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (t + 1 <= t_last) issue(buf1, t + 1);
-    compute(buf0, t);
-    if (t + 1 > t_last) break;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (t + 2 <= t_last) issue(buf0, t + 2);
-    compute(buf1, t + 1);
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no DMA left in flight at exit
-
-  if (ntok == 0) return;
-  PF3_DRAIN();
-  const float sink = sinks ? sinks[head] * 1.4426950408889634f : NEG_INF;
-#pragma unroll
-  for (int nb = 0; nb < 4; ++nb) {
-    float den = lsum[nb] + __shfl_xor(lsum[nb], 16, 64);
-    den += __shfl_xor(den, 32, 64);
-    if (sinks) den += exp2f(sink - (m[nb] == NEG_INF ? 0.f : m[nb]));
-    const float inv = den > 0.f ? vscale / den : 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      float x[NB];
-      if (nb == 0) {
-        if (i == 0) { PF3_READ_0_0(x) } else if (i == 1) { PF3_READ_0_1(x) } else if (i == 2) { PF3_READ_0_2(x) } else { PF3_READ_0_3(x) }
-      } else if (nb == 1) {
-        if (i == 0) { PF3_READ_1_0(x) } else if (i == 1) { PF3_READ_1_1(x) } else if (i == 2) { PF3_READ_1_2(x) } else { PF3_READ_1_3(x) }
-      } else if (nb == 2) {
-        if (i == 0) { PF3_READ_2_0(x) } else if (i == 1) { PF3_READ_2_1(x) } else if (i == 2) { PF3_READ_2_2(x) } else { PF3_READ_2_3(x) }
-      } else {
-        if (i == 0) { PF3_READ_3_0(x) } else if (i == 1) { PF3_READ_3_1(x) } else if (i == 2) { PF3_READ_3_2(x) } else { PF3_READ_3_3(x) }
-      }
-      const float f = __shfl(inv, 4 * g + i, 64);
-      const int tk = tok0 + 16 * nb + 4 * g + i;
-      if (tk < ql) {
-        uint16_t* orow = out + (int64_t)(qs + tk) * out_stride + (int64_t)head * D;
-#pragma unroll
-        for (int n = 0; n < NB; ++n) orow[16 * n + c16] = f2bf(x[n] * f);
-      }
-    }
-  }
-}
-
 
 // ---------------------------------------------------------------- v4 (bf16 cache, D = 128): 32x32x16 MFMAs
 // The work decomposition, items, K/V tiles and the double-buffered LDS-DMA ring of v2; the two
@@ -1387,33 +1061,7 @@ __global__ __launch_bounds__(NT, 2) void prefill_v4_kernel(
       }
   }
 }
-}  // namespace
 
-// v3 for D = 128 bf16 caches with blocks of >= 64 keys and whole groups of 4 query
-// heads per KV head (LLMD_PREFILL_V3=1 until its GPU numerics have run on the
-// driver's box; v2 otherwise); the single source of the item shape
-static bool prefill_v3_ok(int Hq, int Hkv, int D, int bs, int fp8) {
-  static const bool off = [] {
-    const char* e = getenv("LLMD_PREFILL_V3");
-    return !(e && e[0] == '1');
-  }();
-  static const bool v1_only = [] {
-    const char* e = getenv("LLMD_PREFILL_V1");
-    return e && e[0] == '1';
-  }();
-  return !off && !v1_only && D == 128 && !fp8 && bs >= 64 && Hkv > 0 && (Hq / Hkv) % 4 == 0;
-}
-
-
-
-// v4 (32x32x16 MFMAs) for D = 128 bf16 caches: LLMD_PREFILL_V4=1 (off until its GPU A/B); read per
-// launch so one process can A/B both (v4 and v2 share the item shape)
-static bool prefill_v4_on() {
-  const char* e = getenv("LLMD_PREFILL_V4");
-  return e && e[0] == '1';
-}
-
-namespace {
 // The K / V blocks a prefill step reads from an fp8 (e4m3) paged cache, widened exactly into a dense
 // bf16 copy (block table entry e -> row e of the copy): the fp8-KV prefill then runs on the bf16 v2
 // kernel (k_scale folded into its softmax scale, v_scale into its epilogue, as for the fp8 kernel)
@@ -1441,6 +1089,13 @@ extern "C" int llmd_kv_dequant_gather(const void* kc, const void* vc, int64_t bl
   hipLaunchKernelGGL(kv_dequant_gather_kernel, dim3(n_entries, 2), dim3(256), 0, st, (const uint8_t*)kc,
                      (const uint8_t*)vc, block_stride, bt, n_blocks, per_block, (uint16_t*)kd, (uint16_t*)vd);
   return (int)hipGetLastError();
+}
+
+// v4 (32x32x16 MFMAs) for D = 128 bf16 caches: LLMD_PREFILL_V4=1 (off until its GPU A/B); read per
+// launch so one process can A/B both (v4 and v2 share the item shape)
+static bool prefill_v4_on() {
+  const char* e = getenv("LLMD_PREFILL_V4");
+  return e && e[0] == '1';
 }
 
 // the software-pipelined v5 (csrc/ops/attn_prefill5.hip): 1 when the shape is not covered
@@ -1490,17 +1145,11 @@ extern "C" int llmd_paged_prefill(const void* q, int64_t q_stride, const void* k
     const char* e = getenv("LLMD_PREFILL_XCD");
     return !(e && e[0] == '0');
   }();
-  if (prefill_v3_ok(Hq, Hkv, D, bs, fp8)) {
-    const dim3 grid3(n_items, Hkv * (G / 4));
-    hipLaunchKernelGGL(prefill_v3_kernel, grid3, blk, 0, st, (const uint16_t*)q, q_stride, (const uint16_t*)kc,
-                       (const uint16_t*)vc, block_stride, bs, block_tables, bt_stride, q_start, q_len, ctx_len,
-                       items, Hq, Hkv, G, scale_log2, window, sinks, (uint16_t*)out, out_stride, v_scale,
-                       xcd_map && (int64_t)n_items * grid3.y >= 1024 ? 1 : 0);
-  } else if (!fp8 && !v1_only && prefill_v5_on() &&
-             llmd_paged_prefill_v5(q, q_stride, kc, vc, block_stride, bs, block_tables, bt_stride, q_start, q_len,
-                                   ctx_len, items, n_items, Hq, Hkv, D, scale_log2, window, sinks, out, out_stride,
-                                   v_scale, xcd_map && (int64_t)n_items * (Hkv * (G / 4)) >= 1024 ? 1 : 0,
-                                   st) == 0) {
+  if (!fp8 && !v1_only && prefill_v5_on() &&
+      llmd_paged_prefill_v5(q, q_stride, kc, vc, block_stride, bs, block_tables, bt_stride, q_start, q_len,
+                            ctx_len, items, n_items, Hq, Hkv, D, scale_log2, window, sinks, out, out_stride,
+                            v_scale, xcd_map && (int64_t)n_items * (Hkv * (G / 4)) >= 1024 ? 1 : 0,
+                            st) == 0) {
     // launched by v5
   } else if (D == 128 && !fp8 && bs >= 16 && !v1_only && prefill_v4_on()) {
     const char* e4 = getenv("LLMD_PREFILL_V4_VARIANT");  // 1: builtin DMA, 3: asm DMA, 7: asm DMA + pipelined halves
@@ -1511,34 +1160,7 @@ extern "C" int llmd_paged_prefill(const void* q, int64_t q_stride, const void* k
                        items, Hq, Hkv, G, HPW, scale_log2, window, sinks, (uint16_t*)out, out_stride, v_scale,
                        xcd_map && (int64_t)n_items * grid.y >= 1024 ? 1 : 0);
   } else if ((D == 128 || D == 64) && !fp8 && bs >= 16 && !v1_only) {
-    const int pv = [] {  // read per launch (tests and A/Bs switch it in one process; getenv is ~0.1 us)
-      // A/B of the round-4 schedule (V above; profiles/attn_prefill_r4_ab.txt): the ring wins everywhere,
-      // the asm DMA only at full ISL and loses 12 % on one-wave grids (5000 x 512 chunk); reading
-      // 6 fragments ahead (bit 2) adds ~1 % -> 5
-      // round 6 (profiles/attn_prefill_v2_variants_r6.txt): unpacked row sums + buffer-descriptor DMA
-      // (bits 4, 5) +1 to +4 % at ISL 2048-8192 -> 53
-      // round 6 (r6w): + Q pre-scaled / accumulators started at -m and row sums on the MFMA (bits 7, 8)
-      // +3 to +6 % more at D = 128, +7 to +9 % over the round-5 V5 at D = 64 (gpt-oss) -> 437 for both
-      const char* e = getenv("LLMD_PREFILL_V2_VARIANT");
-      return e ? (atoi(e) & 511) : -1;
-    }();
-    auto pick = [](int v, bool d128) {  // instantiated: 0-3, 5 (PF 6), 9 (early V), 13 (both); D 128: 21, 37, 53, 69, 117, 181, 309, 437
-      if (d128) return v == 0 ? prefill_v2_kernel<128, 0> : v == 2 ? prefill_v2_kernel<128, 2>
-                     : v == 3 ? prefill_v2_kernel<128, 3> : v == 5 ? prefill_v2_kernel<128, 5>
-                     : v == 9 ? prefill_v2_kernel<128, 9> : v == 13 ? prefill_v2_kernel<128, 13>
-                     : v == 21 ? prefill_v2_kernel<128, 21> : v == 37 ? prefill_v2_kernel<128, 37>
-                     : v == 53 ? prefill_v2_kernel<128, 53> : v == 69 ? prefill_v2_kernel<128, 69>
-                     : v == 117 ? prefill_v2_kernel<128, 117> : v == 181 ? prefill_v2_kernel<128, 181>
-                     : v == 309 ? prefill_v2_kernel<128, 309> : v == 437 ? prefill_v2_kernel<128, 437>
-                     : prefill_v2_kernel<128, 1>;
-      return v == 0 ? prefill_v2_kernel<64, 0> : v == 2 ? prefill_v2_kernel<64, 2>
-             : v == 3 ? prefill_v2_kernel<64, 3> : v == 5 ? prefill_v2_kernel<64, 5>
-             : v == 9 ? prefill_v2_kernel<64, 9> : v == 13 ? prefill_v2_kernel<64, 13>
-             : v == 53 ? prefill_v2_kernel<64, 53> : v == 181 ? prefill_v2_kernel<64, 181>
-             : v == 437 ? prefill_v2_kernel<64, 437>
-             : prefill_v2_kernel<64, 1>;
-    };
-    auto kern = pick(pv >= 0 ? pv : 437, D == 128);
+    auto kern = D == 128 ? prefill_v2_kernel<128> : prefill_v2_kernel<64>;
     hipLaunchKernelGGL(kern, grid, blk, 0, st, (const uint16_t*)q, q_stride, (const uint16_t*)kc,
                        (const uint16_t*)vc, block_stride, bs, block_tables, bt_stride, q_start, q_len, ctx_len,
                        items, Hq, Hkv, G, HPW, scale_log2, window, sinks, (uint16_t*)out, out_stride, v_scale,
@@ -1554,11 +1176,9 @@ extern "C" int llmd_paged_prefill(const void* q, int64_t q_stride, const void* k
   return 0;
 }
 
-// tokens per work item (host helper, mirrors the kernel llmd_paged_prefill
-// dispatches: v3 64; v1 / v2 32 query tokens per wave, 4 / HPW waves stacked
-// along the tokens)
-extern "C" int llmd_prefill_tokens_per_item(int Hq, int Hkv, int D, int bs, int fp8) {
-  if (prefill_v3_ok(Hq, Hkv, D, bs, fp8)) return 64;  // v3: 64 tokens x 4 heads per workgroup
+// tokens per work item (host helper; both kernels: 32 query tokens per wave,
+// 4 / HPW waves stacked along the tokens)
+extern "C" int llmd_prefill_tokens_per_item(int Hq, int Hkv, int /*D*/, int /*bs*/, int /*fp8*/) {
   const int G = Hq / Hkv;
   const int HPW = (G % 4 == 0) ? 4 : ((G % 2 == 0) ? 2 : 1);
   return 32 * (4 / HPW);

@@ -1,5 +1,5 @@
 """Run only the GQA prefill attention at ISL 5000 (Llama-3-70B heads 64/8, D 128, block 64) a
-fixed number of times - the target of a rocprofv3 --pmc pass (variant: LLMD_PREFILL_V2_VARIANT).
+fixed number of times - the target of a rocprofv3 --pmc pass.
   python scripts/attn_only.py [iters]"""
 import os
 import sys
