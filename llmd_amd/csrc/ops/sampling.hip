@@ -21,10 +21,11 @@ __device__ __forceinline__ uint64_t mix64(uint64_t z) {
   z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
   return z ^ (z >> 31);
 }
-// uniform in (0, 1)
+// uniform in (0, 1). 0xFFFFFF + 0.5 is no float and rounds up to 2^24, i.e. u == 1 and a
+// Gumbel key of +inf that wins whatever its logit: clamp to the largest float below 1.
 __device__ __forceinline__ float uniform01(uint64_t seed, uint64_t idx) {
   const uint64_t h = mix64(seed ^ mix64(idx + 0x9e3779b97f4a7c15ull));
-  return ((float)(h >> 40) + 0.5f) * (1.0f / 16777216.0f);
+  return fminf(((float)(h >> 40) + 0.5f) * (1.0f / 16777216.0f), 0x1.fffffep-1f);
 }
 
 struct Best {

@@ -174,6 +174,8 @@ def sample(logits, temps=None, generator=None):
 
 
 def topk_topp_mask(logits, topk=None, topp=None, temps=None):
+    """In-place top-k then top-p (vLLM order): the top-p mass is taken over the top-k
+    survivors, renormalised. Ties with the threshold value are kept."""
     lf = logits
     B, V = lf.shape
     for b in range(B):
@@ -186,7 +188,7 @@ def topk_topp_mask(logits, topk=None, topp=None, temps=None):
             thr = torch.topk(row, k).values[-1]
             keep &= row >= thr
         if p < 1.0:
-            probs = torch.softmax(row / t, -1)
+            probs = torch.softmax(row.masked_fill(~keep, float("-inf")) / t, -1)
             sp, idx = torch.sort(probs, descending=True)
             cum = torch.cumsum(sp, 0)
             n = int((cum < p).sum().item()) + 1
