@@ -37,6 +37,8 @@ void llmd_sample(const void*, int64_t, int, int, int, const float*, const int64_
 int llmd_sample_splits(int, int);
 void llmd_topk_topp_mask(float*, int64_t, int, int, const int*, const float*, const float*,
                          hipStream_t);
+void llmd_top_logprobs(const void*, int64_t, int, int, int, const int*, int, int*, float*, hipStream_t);
+int llmd_top_logprobs_max();
 int llmd_kvx_copy_blocks(void*, const void*, int64_t, int64_t, const int*, int, const int64_t*, int,
                          int64_t, hipStream_t);
 int llmd_kvx_copy_blocks2(void*, const void*, int64_t, int64_t, const int*, int, const int64_t*, int, int64_t, int,
@@ -738,6 +740,27 @@ void topk_topp_mask(torch::Tensor logits, c10::optional<torch::Tensor> topk,
   llmd_topk_topp_mask(logits.data_ptr<float>(), logits.stride(0), B, V, k, p, t, cur_stream());
 }
 
+// top-n alternatives of every row: out_ids / out_lp [B, llmd_top_logprobs_max()], n_per_row int32 [B]
+void top_logprobs(torch::Tensor logits, torch::Tensor n_per_row, torch::Tensor out_ids, torch::Tensor out_lp) {
+  const c10::hip::OptionalHIPGuard device_guard(dev_of(logits));
+  CHECK_CUDA(logits); CHECK_INNER(logits);
+  TORCH_CHECK(logits.dim() == 2, "logits 2-D");
+  const bool bf = logits.scalar_type() == at::kBFloat16;
+  TORCH_CHECK(bf || logits.scalar_type() == at::kFloat, "logits bf16/f32");
+  const int B = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(logits.stride(0) % (bf ? 8 : 4) == 0 && (uintptr_t)logits.data_ptr() % 16 == 0,
+              "16-B aligned logits rows");
+  const int nmax = llmd_top_logprobs_max();
+  CHECK_CUDA(n_per_row); CHECK_DT(n_per_row, at::kInt);
+  TORCH_CHECK(n_per_row.is_contiguous() && n_per_row.numel() >= B, "n_per_row");
+  CHECK_CUDA(out_ids); CHECK_DT(out_ids, at::kInt);
+  CHECK_CUDA(out_lp); CHECK_DT(out_lp, at::kFloat);
+  TORCH_CHECK(out_ids.is_contiguous() && out_ids.numel() >= (int64_t)B * nmax, "out_ids [B, MAX_TOP_LOGPROBS]");
+  TORCH_CHECK(out_lp.is_contiguous() && out_lp.numel() >= (int64_t)B * nmax, "out_lp [B, MAX_TOP_LOGPROBS]");
+  llmd_top_logprobs(logits.data_ptr(), logits.stride(0), B, V, bf ? 1 : 0, n_per_row.data_ptr<int>(), nmax,
+                    out_ids.data_ptr<int>(), out_lp.data_ptr<float>(), cur_stream());
+}
+
 // ---------------------------------------------------------------- kvx
 // dst/src are base addresses of the two KV pools (src may be an IPC-mapped peer pointer)
 void kvx_copy_blocks(torch::Tensor dst, int64_t src_ptr, int64_t dst_stride, int64_t src_stride,
@@ -1289,6 +1312,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {  // _C, or _C_debug (llmd_amd/build.p
   });
   m.def("sample", &sample);
   m.def("topk_topp_mask", &topk_topp_mask);
+  m.def("top_logprobs", &top_logprobs);
+  m.def("top_logprobs_max", &llmd_top_logprobs_max);
   m.def("kvx_copy_blocks", &kvx_copy_blocks);
   m.def("kvx_dma_blocks", &kvx_dma_blocks);
   m.def("kvx_ipc_export", &kvx_ipc_export);

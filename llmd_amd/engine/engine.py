@@ -318,6 +318,8 @@ class LLMEngine:
             o = RequestOutput(r.request_id, [r.output_token_ids[-1]], [r.output_logprobs[-1]],
                               r.status.finished, r.finish_reason, r.num_prompt_tokens,
                               len(r.output_token_ids), r.num_cached_tokens)
+            if r.params.top_logprobs:
+                o.new_top_logprobs = [r.output_top_logprobs[-1]]
             if r.status.finished:
                 o.kv_transfer_params = r.extra.get("kv_transfer_params_out")
                 o.embedding = r.extra.get("embedding")

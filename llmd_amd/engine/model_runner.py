@@ -50,12 +50,14 @@ class DeferredSample:
     for the next step's decode inputs; a non-blocking copy to pinned host memory plus an
     event let ``host()`` wait for exactly this step, not for the step launched after it."""
 
-    __slots__ = ("ids", "lp", "seq_ids", "row_of", "_h_ids", "_h_lp", "_ev")
+    __slots__ = ("ids", "lp", "seq_ids", "row_of", "_h_ids", "_h_lp", "_h_top", "_top_n", "_ev")
 
-    def __init__(self, ids, lp, seq_ids, gpu: bool):
+    def __init__(self, ids, lp, seq_ids, gpu: bool, top=None):
+        """``top``: None, or (ids [B, N], logprobs [B, N], per-row counts) of ops.top_logprobs."""
         self.ids, self.lp, self.seq_ids = ids, lp, seq_ids
         self.row_of = {s: i for i, s in enumerate(seq_ids)}
         self._ev = None
+        self._h_top, self._top_n = None, (top[2] if top is not None else None)
         if gpu and ids is not None:
             self._h_ids = torch.empty(ids.shape, dtype=ids.dtype, pin_memory=True)
             self._h_ids.copy_(ids, non_blocking=True)
@@ -63,10 +65,16 @@ class DeferredSample:
             if lp is not None:
                 self._h_lp = torch.empty(lp.shape, dtype=lp.dtype, pin_memory=True)
                 self._h_lp.copy_(lp, non_blocking=True)
+            if top is not None:
+                self._h_top = tuple(torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for t in top[:2])
+                for h, t in zip(self._h_top, top[:2]):
+                    h.copy_(t, non_blocking=True)
             self._ev = torch.cuda.Event()
             self._ev.record()
         else:
             self._h_ids, self._h_lp = ids, lp
+            if top is not None:
+                self._h_top = (top[0], top[1])
 
     @classmethod
     def empty(cls) -> "DeferredSample":
@@ -77,9 +85,22 @@ class DeferredSample:
             return {}
         if self._ev is not None:
             self._ev.synchronize()
-        ids = self._h_ids.tolist()
-        lp = self._h_lp.tolist() if self._h_lp is not None else [0.0] * len(ids)
-        return {s: (int(ids[i]), float(lp[i])) for i, s in enumerate(self.seq_ids)}
+        top = (self._h_top[0], self._h_top[1], self._top_n) if self._h_top is not None else None
+        return _host_samples(self._h_ids, self._h_lp, top, self.seq_ids)
+
+
+def _host_samples(ids, lp, top, seq_ids) -> dict:
+    """seq_id -> (token, logprob), or (token, logprob, [(token id, logprob), ...]) for the rows
+    that asked for alternatives (``top``: ids, logprobs, per-row counts; unused slots are -1)."""
+    ids_h = ids.tolist()
+    lp_h = lp.tolist() if lp is not None else [0.0] * len(ids_h)
+    out = {s: (int(ids_h[i]), float(lp_h[i])) for i, s in enumerate(seq_ids)}
+    if top is not None:
+        t_ids, t_lp, t_n = top[0].tolist(), top[1].tolist(), top[2]
+        for i, s in enumerate(seq_ids):
+            if t_n[i] > 0:
+                out[s] += ([(t, l) for t, l in zip(t_ids[i][:t_n[i]], t_lp[i][:t_n[i]]) if t >= 0],)
+    return out
 
 
 def _mix64(z: int) -> int:
@@ -532,10 +553,10 @@ class ModelRunner:
                 if r.params.embed:
                     r.extra["embedding"] = e[i].tolist()
         with markers.range("llmd.sample"):
-            ids, lp = self._sample_dev(logits, reqs)
+            ids, lp, top = self._sample_dev(logits, reqs)
             if defer:
-                return DeferredSample(ids, lp, [r.seq_id for r in reqs], self.is_gpu)
-            return self._to_host(ids, lp, reqs)
+                return DeferredSample(ids, lp, [r.seq_id for r in reqs], self.is_gpu, top)
+            return self._to_host(ids, lp, reqs, top)
 
     def _gather_from(self, so: SchedulerOutput, prev: "DeferredSample"):
         """(dst rows, src rows) device index tensors: decode rows whose input token is the
@@ -670,18 +691,22 @@ class ModelRunner:
         return logits
 
     def _sample(self, logits, reqs):
-        ids, lp = self._sample_dev(logits, reqs)
-        return self._to_host(ids, lp, reqs)
+        ids, lp, top = self._sample_dev(logits, reqs)
+        return self._to_host(ids, lp, reqs, top)
 
     @staticmethod
-    def _to_host(ids, lp, reqs):
-        ids_h = ids.cpu().tolist()
-        lp_h = lp.cpu().tolist() if lp is not None else [0.0] * len(ids_h)
-        return {r.seq_id: (int(ids_h[i]), float(lp_h[i])) for i, r in enumerate(reqs)}
+    def _to_host(ids, lp, reqs, top=None):
+        if top is not None:
+            top = (top[0].cpu(), top[1].cpu(), top[2])
+        return _host_samples(ids.cpu(), lp.cpu() if lp is not None else None, top, [r.seq_id for r in reqs])
 
     def _sample_dev(self, logits, reqs):
+        """(ids, logprob or None, top or None); ``top`` = (ids, logprobs, per-row counts) of
+        ops.top_logprobs on the logits the sampler saw, only when a request asks for alternatives."""
         temps, seeds, topk, topp, any_rand, any_k, any_p = self._sampling_tensors(reqs)
-        want_lp = any(r.params.logprobs for r in reqs)
+        top_n = [r.params.top_logprobs for r in reqs]
+        want_top = any(top_n)
+        want_lp = want_top or any(r.params.logprobs for r in reqs)
         dev = self.device
         if any(r.params.penalized for r in reqs):
             logits = self._penalize(logits, reqs)
@@ -695,7 +720,12 @@ class ModelRunner:
         gen = None
         if not self.is_gpu and any_rand:
             gen = torch.Generator().manual_seed(int(seeds[0]) & 0x7FFFFFFF)
-        return ops.sample(logits, t, s, want_logprob=want_lp, generator=gen)
+        ids, lp = ops.sample(logits, t, s, want_logprob=want_lp, generator=gen)
+        if not want_top:
+            return ids, lp, None
+        n = torch.tensor(top_n, dtype=torch.int32).to(logits.device, non_blocking=True)
+        t_ids, t_lp = ops.top_logprobs(logits, n)
+        return ids, lp, (t_ids, t_lp, top_n)
 
     def _run_eager(self, pl: dict):
         ids, meta = self._eager_meta(pl)

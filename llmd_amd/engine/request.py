@@ -27,6 +27,7 @@ class SamplingParams:
     repetition_penalty: float = 1.0    # vLLM/HF: logits of prompt+output tokens / r (if > 0) or x r
     min_p: float = 0.0                 # drop tokens with prob < min_p x max prob
     logit_bias: Optional[dict] = None  # token id -> additive bias
+    top_logprobs: int = 0              # OpenAI: the N most likely alternatives of every output token (<= 20)
 
     @property
     def penalized(self) -> bool:
@@ -47,6 +48,18 @@ class SamplingParams:
         def g(k, d):
             v = body.get(k)
             return d if v is None else v
+        # logprobs: chat form `logprobs: true` (+ `top_logprobs: N`), completions form `logprobs: N`
+        lp = body.get("logprobs")
+        lp = lp if isinstance(lp, int) else None  # a bool is an int: `true` alone = sampled token only
+        top = body.get("top_logprobs")
+        if top is not None:
+            if isinstance(top, bool) or not isinstance(top, int):
+                raise ValueError(f"top_logprobs must be an integer, got {top!r}")
+            if not lp:
+                raise ValueError("top_logprobs requires logprobs to be set")
+            lp = 1
+        elif lp is not None and not isinstance(lp, bool):
+            top = lp
         sp = cls(
             max_tokens=int(mt) if mt is not None else default_max,
             temperature=float(body.get("temperature", 1.0) if body.get("temperature") is not None else 1.0),
@@ -57,14 +70,14 @@ class SamplingParams:
             stop_token_ids=list(body.get("stop_token_ids") or []),
             stop=stop,
             ignore_eos=bool(body.get("ignore_eos", False)),
-            logprobs=body.get("logprobs") if isinstance(body.get("logprobs"), int) else (
-                1 if body.get("logprobs") is True else None),
+            logprobs=lp,
             n=int(g("n", 1)),
             presence_penalty=float(g("presence_penalty", 0.0)),
             frequency_penalty=float(g("frequency_penalty", 0.0)),
             repetition_penalty=float(g("repetition_penalty", 1.0)),
             min_p=float(g("min_p", 0.0)),
             logit_bias={int(k): float(v) for k, v in (body.get("logit_bias") or {}).items()} or None,
+            top_logprobs=top or 0,
         )._validated()
         return sp.check_vocab(vocab_size) if vocab_size else sp
 
@@ -78,6 +91,8 @@ class SamplingParams:
             raise ValueError(f"repetition_penalty must be > 0, got {self.repetition_penalty}")
         if not 0.0 <= self.min_p <= 1.0:
             raise ValueError(f"min_p must be in [0, 1], got {self.min_p}")
+        if not 0 <= self.top_logprobs <= 20:
+            raise ValueError(f"top_logprobs must be in [0, 20], got {self.top_logprobs}")
         if not 1 <= self.n <= 128:
             raise ValueError(f"n must be in [1, 128], got {self.n}")
         if self.max_tokens < 0 or self.temperature < 0 or not 0.0 < self.top_p <= 1.0:
@@ -155,6 +170,9 @@ class Request:
     # (max_tokens / max_model_len reached), so the request is not scheduled again
     async_pending: bool = False
     final_pending: bool = False
+    # per output token: None, or the params.top_logprobs most likely (token id, logprob) pairs
+    # (fewer when the row had fewer unmasked entries)
+    output_top_logprobs: list = field(default_factory=list)
 
     @property
     def cache_extra(self) -> int:
@@ -215,3 +233,4 @@ class RequestOutput:
     embedding: Optional[list] = None
     ttft: Optional[float] = None
     metrics: Optional[dict] = None
+    new_top_logprobs: Optional[list] = None  # per new token, for requests with top_logprobs > 0

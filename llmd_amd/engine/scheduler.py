@@ -420,7 +420,8 @@ class Scheduler:
                 break
 
     def update(self, out: SchedulerOutput, sampled: dict[int, tuple[int, float]]) -> list[Request]:
-        """Apply a step's results. `sampled`: seq_id -> (token, logprob).
+        """Apply a step's results. `sampled`: seq_id -> (token, logprob) or, for a request with
+        top_logprobs, (token, logprob, [(token id, logprob), ...]).
         Returns requests that produced new tokens or finished this step."""
         touched = []
         now = time.monotonic()
@@ -445,9 +446,10 @@ class Scheduler:
                     n_keep -= 1
                 self.bm.after_compute(r.seq_id, n_keep)
             if r.seq_id in sampled:
-                tok, lp = sampled[r.seq_id]
+                tok, lp, *rest = sampled[r.seq_id]
                 r.output_token_ids.append(tok)
                 r.output_logprobs.append(lp)
+                r.output_top_logprobs.append(rest[0] if rest else None)
                 if r.first_token_time is None:
                     r.first_token_time = now
                 r.last_token_time = now
@@ -486,6 +488,7 @@ class Scheduler:
             if r.seq_id in sampling:
                 r.output_token_ids.append(self.PLACEHOLDER)
                 r.output_logprobs.append(0.0)
+                r.output_top_logprobs.append(None)
                 r.async_pending = True
                 # the token in flight is the last one whatever its value: do not schedule again
                 if len(r.output_token_ids) >= r.params.max_tokens or r.num_tokens >= self.sc.max_model_len:
@@ -499,9 +502,10 @@ class Scheduler:
             if r.status.finished:
                 continue
             if r.seq_id in sampled and r.async_pending:
-                tok, lp = sampled[r.seq_id]
+                tok, lp, *rest = sampled[r.seq_id]
                 r.output_token_ids[-1] = tok
                 r.output_logprobs[-1] = lp
+                r.output_top_logprobs[-1] = rest[0] if rest else None
                 r.async_pending = False
                 if r.first_token_time is None:
                     r.first_token_time = now

@@ -974,6 +974,25 @@ def topk_topp_mask(logits, topk=None, topp=None, temps=None):
     return logits
 
 
+MAX_TOP_LOGPROBS = ref.MAX_TOP_LOGPROBS  # the OpenAI limit of top_logprobs (NMAX of logprobs.hip)
+
+
+def top_logprobs(logits, n_per_row):
+    """The ``n_per_row[r]`` most likely tokens of every row (value descending, lower vocabulary
+    index first among equals) with their log-softmax over the whole row, no temperature:
+    ``(ids int32 [B, MAX_TOP_LOGPROBS], lp f32 [B, MAX_TOP_LOGPROBS])``. Masked (-inf) entries
+    are never reported; unused slots hold ``-1 / -inf``. ``n_per_row``: int32 on the logits' device."""
+    if not _gpu(logits):
+        return ref.top_logprobs(logits, n_per_row)
+    C = native()
+    assert C.top_logprobs_max() == MAX_TOP_LOGPROBS
+    B = logits.shape[0]
+    ids = torch.empty(B, MAX_TOP_LOGPROBS, dtype=torch.int32, device=logits.device)
+    lp = torch.empty(B, MAX_TOP_LOGPROBS, dtype=torch.float32, device=logits.device)
+    C.top_logprobs(logits, n_per_row, ids, lp)
+    return ids, lp
+
+
 rope_cos_sin = ref.rope_cos_sin
 
 

@@ -173,6 +173,26 @@ def sample(logits, temps=None, generator=None):
     return ids, logp.gather(-1, ids[:, None]).squeeze(-1)
 
 
+MAX_TOP_LOGPROBS = 20
+
+
+def top_logprobs(logits, n_per_row):
+    """Top-n alternatives per row: log-softmax in fp32, a stable descending sort (lower index
+    first among equal values), -inf entries never reported, unused slots ``-1 / -inf``."""
+    lf = logits.float()
+    B, V = lf.shape
+    logp = torch.log_softmax(lf, -1)
+    vals, order = torch.sort(lf, dim=-1, descending=True, stable=True)
+    w = min(V, MAX_TOP_LOGPROBS)
+    ids = torch.full((B, MAX_TOP_LOGPROBS), -1, dtype=torch.int32, device=lf.device)
+    lp = torch.full((B, MAX_TOP_LOGPROBS), float("-inf"), dtype=torch.float32, device=lf.device)
+    n = n_per_row.to(lf.device).long().clamp(0, MAX_TOP_LOGPROBS)
+    live = (torch.arange(w, device=lf.device)[None, :] < n[:, None]) & (vals[:, :w] > float("-inf"))
+    ids[:, :w] = torch.where(live, order[:, :w].to(torch.int32), ids[:, :w])
+    lp[:, :w] = torch.where(live, logp.gather(-1, order[:, :w]), lp[:, :w])
+    return ids, lp
+
+
 def topk_topp_mask(logits, topk=None, topp=None, temps=None):
     """In-place top-k then top-p (vLLM order): the top-p mass is taken over the top-k
     survivors, renormalised. Ties with the threshold value are kept."""

@@ -254,6 +254,43 @@ class OpenAIServer:
             return int(body["priority"])
         return 0
 
+    # ------------------------------------------------------------ logprobs
+    @staticmethod
+    def _new_tops(o) -> list:
+        """Per new token of a step output: None or its [(token id, logprob), ...] alternatives."""
+        return getattr(o, "new_top_logprobs", None) or [None] * len(o.new_token_ids)
+
+    def _completion_logprobs(self, toks, lps, tops, want_top: bool, offset: int = 0) -> dict:
+        """/v1/completions ``logprobs`` object of the tokens ``toks``; ``offset``: characters
+        of the choice's text before them (streaming)."""
+        strs = [self.tok.decode([t]) for t in toks]
+        out = {"token_logprobs": list(lps), "tokens": strs}
+        top = None
+        if want_top:
+            top = []
+            for alts in tops:
+                d: dict = {}
+                for t, lp in alts or []:
+                    k = self.tok.decode([t])
+                    if k not in d or lp > d[k]:  # two ids with one string: the likelier one
+                        d[k] = lp
+                top.append(d)
+        out["top_logprobs"] = top
+        offs = []
+        for k in strs:
+            offs.append(offset)
+            offset += len(k)
+        out["text_offset"] = offs
+        return out
+
+    def _chat_logprobs(self, toks, lps, tops) -> dict:
+        """/v1/chat/completions ``logprobs`` object of the tokens ``toks``."""
+        def ent(t, lp):
+            k = self.tok.decode([t])
+            return {"token": k, "logprob": lp, "bytes": list(k.encode("utf-8"))}
+        return {"content": [dict(ent(t, lp), top_logprobs=[ent(a, alp) for a, alp in alts or []])
+                            for t, lp, alts in zip(toks, lps, tops)]}
+
     # ------------------------------------------------------------ completions
     async def completions(self, req: web.Request):
         return await self._serve(req, chat=False)
@@ -321,16 +358,17 @@ class OpenAIServer:
                                       include_usage, created, model_name, mm, tools_on, rid_base)
 
         async def one(k, ids, pk):
-            text_ids, lps, last = [], [], None
+            text_ids, lps, tops, last = [], [], [], None
             async for o in self.aeng.generate(rids[k], ids, pk, prio, ktp, lora, mm):
                 text_ids.extend(o.new_token_ids)
                 lps.extend(o.new_logprobs)
+                tops.extend(self._new_tops(o))
                 last = o
                 text = self.tok.decode(text_ids)
                 if pk.stop and any(s in text for s in pk.stop):
                     self.aeng.abort(rids[k])
                     break
-            return ids, text_ids, lps, last
+            return ids, text_ids, lps, tops, last
         try:
             results = await asyncio.gather(*[one(k, ids, pk) for k, (ids, pk) in enumerate(jobs)])
         except EngineDeadError as e:
@@ -339,7 +377,7 @@ class OpenAIServer:
             return _err(500, f"{type(e).__name__}: {e}", "InternalServerError")
         choices, n_prompt, n_out = [], 0, 0
         out_ktp = None
-        for i, (ids, toks, lps, last) in enumerate(results):
+        for i, (ids, toks, lps, tops, last) in enumerate(results):
             text = self.tok.decode(toks)
             finish = last.finish_reason if last is not None else "abort"
             if params.stop:
@@ -363,10 +401,12 @@ class OpenAIServer:
                     if calls:
                         ch["finish_reason"] = "tool_calls"
                 ch["message"] = msg
+                if params.logprobs:  # not requested: no key, as before (a client reads it as null)
+                    ch["logprobs"] = self._chat_logprobs(toks, lps, tops)
             else:
                 ch["text"] = text
                 if params.logprobs:
-                    ch["logprobs"] = {"token_logprobs": lps, "tokens": [self.tok.decode([t]) for t in toks]}
+                    ch["logprobs"] = self._completion_logprobs(toks, lps, tops, params.top_logprobs > 0)
             if body.get("return_token_ids"):
                 ch["token_ids"] = toks
             choices.append(ch)
@@ -409,17 +449,32 @@ class OpenAIServer:
 
         async def one_choice(idx, crid, params):
             toks: list[int] = []
+            lps: list[float] = []
+            tops: list = []
             sent = ""
             n_emitted = 0
+            n_chars = 0  # characters of the tokens already reported (completions text_offset)
             if chat:
                 await send(chunk(idx, {"delta": {"role": "assistant", "content": ""}}, None))
             st = self.parser.streamer(tools_on) if (chat and self.parser is not None) else None
             every = max(1, int(self.opts.stream_interval))
             async for o in self.aeng.generate(crid, ids, params, prio, ktp, lora, mm):
                 toks.extend(o.new_token_ids)
+                if params.logprobs:
+                    lps.extend(o.new_logprobs)
+                    tops.extend(self._new_tops(o))
                 n_outs[idx] = len(toks)
                 if not o.finished and len(toks) - n_emitted < every:  # --stream-interval
                     continue
+                lp_obj = None  # log-probabilities of exactly the tokens this chunk newly covers
+                if params.logprobs:
+                    new = slice(n_emitted, len(toks))
+                    if chat:
+                        lp_obj = self._chat_logprobs(toks[new], lps[new], tops[new])
+                    else:
+                        lp_obj = self._completion_logprobs(toks[new], lps[new], tops[new],
+                                                           params.top_logprobs > 0, n_chars)
+                        n_chars += sum(len(k) for k in lp_obj["tokens"])
                 n_emitted = len(toks)
                 text = self.tok.decode(toks)
                 stop_hit = False
@@ -438,12 +493,19 @@ class OpenAIServer:
                         deltas += tail
                         if called:
                             finish = "tool_calls"
-                    for k, dl in enumerate(deltas):
-                        await send(chunk(idx, {"delta": dl}, finish if k == len(deltas) - 1 else None))
+                    for k, dl in enumerate(deltas):  # a step split into several deltas: the first carries it
+                        cb = {"delta": dl, "logprobs": lp_obj} if (lp_obj is not None and k == 0) else {"delta": dl}
+                        await send(chunk(idx, cb, finish if k == len(deltas) - 1 else None))
                     if finish is not None and not deltas:
-                        await send(chunk(idx, {"delta": {}}, finish))
+                        await send(chunk(idx, {"delta": {}, "logprobs": lp_obj} if lp_obj is not None
+                                         else {"delta": {}}, finish))
+                    elif lp_obj is not None and not deltas:  # the parser holds the text back: an empty delta
+                        await send(chunk(idx, {"delta": {}, "logprobs": lp_obj}, None))
                 else:
-                    d = chunk(idx, {"delta": {"content": delta}} if chat else {"text": delta}, finish)
+                    cb = {"delta": {"content": delta}} if chat else {"text": delta}
+                    if lp_obj is not None:
+                        cb["logprobs"] = lp_obj
+                    d = chunk(idx, cb, finish)
                     if o.finished and o.kv_transfer_params is not None:
                         d["kv_transfer_params"] = o.kv_transfer_params
                     await send(d)
