@@ -39,6 +39,11 @@ void llmd_topk_topp_mask(float*, int64_t, int, int, const int*, const float*, co
                          hipStream_t);
 void llmd_top_logprobs(const void*, int64_t, int, int, int, const int*, int, int*, float*, hipStream_t);
 int llmd_top_logprobs_max();
+void llmd_guided_mask(void*, int64_t, int, int, int, const uint16_t*, const uint8_t*, int, const int*, const int*,
+                      const int*, const uint8_t*, int64_t, const int*, const int*, int, hipStream_t);
+int llmd_guided_lds_states();
+int llmd_guided_max_eos();
+int llmd_guided_splits(int, int);
 int llmd_kvx_copy_blocks(void*, const void*, int64_t, int64_t, const int*, int, const int64_t*, int,
                          int64_t, hipStream_t);
 int llmd_kvx_copy_blocks2(void*, const void*, int64_t, int64_t, const int*, int, const int64_t*, int, int64_t, int,
@@ -761,6 +766,49 @@ void top_logprobs(torch::Tensor logits, torch::Tensor n_per_row, torch::Tensor o
                     out_ids.data_ptr<int>(), out_lp.data_ptr<float>(), cur_stream());
 }
 
+// guided-decoding mask in place (csrc/ops/guided.hip): trans uint16 [cap, 256] / accept uint8 [cap] the DFA
+// arena, dfa_off / dfa_n / state int32 [B] per row (state -1: row untouched), tok_bytes uint8 + tok_off int32
+// [V + 1] the token byte table. The per-row values are validated on the host by ops.guided_mask.
+void guided_mask(torch::Tensor logits, torch::Tensor trans, torch::Tensor accept, torch::Tensor dfa_off,
+                 torch::Tensor dfa_n, torch::Tensor state, torch::Tensor tok_bytes, torch::Tensor tok_off,
+                 std::vector<int64_t> eos_ids) {
+  const c10::hip::OptionalHIPGuard device_guard(dev_of(logits));
+  CHECK_CUDA(logits); CHECK_INNER(logits);
+  TORCH_CHECK(logits.dim() == 2, "logits 2-D");
+  const bool bf = logits.scalar_type() == at::kBFloat16;
+  TORCH_CHECK(bf || logits.scalar_type() == at::kFloat, "logits bf16/f32");
+  const int64_t B = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(V < (int64_t)1 << 30, "vocabulary too large");
+  TORCH_CHECK(logits.stride(0) % (bf ? 8 : 4) == 0 && (uintptr_t)logits.data_ptr() % 16 == 0,
+              "16-B aligned logits rows");
+  TORCH_CHECK(B <= 1 || logits.stride(0) >= V, "logits rows overlap");
+  CHECK_CUDA(trans); CHECK_DT(trans, at::kUInt16);
+  TORCH_CHECK(trans.dim() == 2 && trans.size(1) == 256 && trans.is_contiguous(), "trans uint16 [cap, 256]");
+  const int64_t cap = trans.size(0);
+  TORCH_CHECK(cap >= 2 && cap < (int64_t)1 << 22, "trans rows");
+  TORCH_CHECK((uintptr_t)trans.data_ptr() % 16 == 0, "16-B aligned trans");
+  CHECK_CUDA(accept); CHECK_DT(accept, at::kByte);
+  TORCH_CHECK(accept.is_contiguous() && accept.numel() >= cap, "accept uint8 [cap]");
+  for (const torch::Tensor* t : {&dfa_off, &dfa_n, &state}) {
+    CHECK_CUDA((*t)); CHECK_DT((*t), at::kInt);
+    TORCH_CHECK(t->is_contiguous() && t->numel() >= B, "dfa_off / dfa_n / state int32 [B]");
+  }
+  CHECK_CUDA(tok_bytes); CHECK_DT(tok_bytes, at::kByte);
+  TORCH_CHECK(tok_bytes.is_contiguous(), "tok_bytes contiguous");
+  CHECK_CUDA(tok_off); CHECK_DT(tok_off, at::kInt);
+  TORCH_CHECK(tok_off.is_contiguous() && tok_off.numel() >= V + 1, "tok_off int32 [V + 1]");
+  TORCH_CHECK((int64_t)eos_ids.size() <= llmd_guided_max_eos(), "too many EOS ids");
+  std::vector<int> eos;
+  for (int64_t e : eos_ids) {
+    TORCH_CHECK(e >= 0 && e < V, "EOS id outside the vocabulary");
+    eos.push_back((int)e);
+  }
+  llmd_guided_mask(logits.data_ptr(), logits.stride(0), (int)B, (int)V, bf ? 1 : 0,
+                   (const uint16_t*)trans.data_ptr(), accept.data_ptr<uint8_t>(), (int)cap, dfa_off.data_ptr<int>(),
+                   dfa_n.data_ptr<int>(), state.data_ptr<int>(), tok_bytes.data_ptr<uint8_t>(), tok_bytes.numel(),
+                   tok_off.data_ptr<int>(), eos.data(), (int)eos.size(), cur_stream());
+}
+
 // ---------------------------------------------------------------- kvx
 // dst/src are base addresses of the two KV pools (src may be an IPC-mapped peer pointer)
 void kvx_copy_blocks(torch::Tensor dst, int64_t src_ptr, int64_t dst_stride, int64_t src_stride,
@@ -1314,6 +1362,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {  // _C, or _C_debug (llmd_amd/build.p
   m.def("topk_topp_mask", &topk_topp_mask);
   m.def("top_logprobs", &top_logprobs);
   m.def("top_logprobs_max", &llmd_top_logprobs_max);
+  m.def("guided_mask", &guided_mask);
+  m.def("guided_lds_states", &llmd_guided_lds_states);
+  m.def("guided_splits", &llmd_guided_splits);
   m.def("kvx_copy_blocks", &kvx_copy_blocks);
   m.def("kvx_dma_blocks", &kvx_dma_blocks);
   m.def("kvx_ipc_export", &kvx_ipc_export);

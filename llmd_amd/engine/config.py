@@ -367,6 +367,8 @@ class EngineConfig:
     enable_lora: bool = False
     max_lora_rank: int = 16
     lora_modules: Optional[dict] = None  # name -> adapter dir, loaded at start-up
+    # structured outputs: DFA states the device arena of compiled grammars holds (513 B each)
+    guided_arena_states: int = 32768
 
     @property
     def served_name(self) -> str:

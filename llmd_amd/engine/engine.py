@@ -61,6 +61,7 @@ class LLMEngine:
 
             self.connector = make_connector(cfg, self)
         self.sched = Scheduler(cfg, self.bm, self.connector)
+        self.sched.on_guided_finish = self._guided_finish
         self.metrics = metrics or EngineMetrics(cfg.served_name, cfg.cache.block_size, nb,
                                                 max_lora=cfg.max_loras if cfg.enable_lora else 0)
         self.event_sink = None  # set by serving.kv_events.KVEventPublisher
@@ -104,13 +105,47 @@ class LLMEngine:
                     arrival_time: Optional[float] = None, mm_inputs: Optional[list] = None) -> Request:
         if params is not None and params.logit_bias:
             params.check_vocab(self.cfg.model_config.vocab_size)
+        if params is not None and params.constrained:
+            self._check_guided(params)
         r = Request(request_id, list(prompt_token_ids), params or SamplingParams(), priority=priority,
                     kv_transfer_params=kv_transfer_params, lora_id=lora_id, mm_inputs=mm_inputs or None)
         if arrival_time is not None:
             r.arrival_time = arrival_time
-        self.sched.add_request(r)
+        if r.params.constrained:
+            self.runner.guided_acquire(r.params.guided)  # ValueError: the arena cannot hold it
+            r.extra["_guided_pinned"] = True
+        try:
+            self.sched.add_request(r)
+        except ValueError:
+            self._guided_finish(r)
+            raise
         self.metrics.on_arrival(r)
         return r
+
+    # ------------------------------------------------------------ structured outputs
+    def set_token_table(self, table) -> None:
+        """The token byte table (llmd_amd.guided.TokenTable over the model's vocabulary) that
+        guided requests are masked and advanced with; refused (ValueError) unless every byte
+        value has a single-byte token."""
+        table.check_guidable()
+        if table.vocab_size < self.cfg.model_config.vocab_size:
+            raise ValueError(f"token table covers {table.vocab_size} ids, the model has "
+                             f"{self.cfg.model_config.vocab_size}")
+        self.runner.token_table = table
+        self.sched.token_table = table
+
+    def _check_guided(self, params: SamplingParams) -> None:
+        if params.ignore_eos:
+            raise ValueError("ignore_eos cannot be combined with a guided-decoding constraint")
+        if self.sched.token_table is None:
+            raise ValueError("guided decoding needs the tokenizer's byte table (LLMEngine.set_token_table)")
+        if not self.cfg.model_config.eos_ids:
+            raise ValueError("guided decoding needs an EOS token id")
+
+    def _guided_finish(self, r: Request) -> None:
+        """A constrained request finished (or was never admitted): unpin its grammar."""
+        if r.extra.pop("_guided_pinned", False):
+            self.runner.guided_release(r.params.guided)
 
     def abort(self, request_id: str):
         r = self.sched.abort(request_id)
@@ -169,15 +204,17 @@ class LLMEngine:
 
     def _needs_settled(self, so) -> bool:
         """Steps whose planning reads output-token VALUES must wait for the step in flight:
-        penalties / logit bias / min-p, embeddings, and a recompute chunk that re-reads a
-        placeholder (a request preempted while its last token was in flight)."""
+        penalties / logit bias / min-p, guided decoding (the DFA state follows the token),
+        embeddings, and a recompute chunk that re-reads a placeholder (a request preempted
+        while its last token was in flight)."""
         for sr in so.decodes:
             sp = sr.req.params
-            if sp.penalized or sp.embed:
+            if sp.penalized or sp.embed or sp.constrained:
                 return True
         for sr in so.prefills:
             r = sr.req
-            if r.params.penalized or r.params.embed or (r.async_pending and sr.start + sr.num_new_tokens >= r.num_tokens):
+            if r.params.penalized or r.params.embed or r.params.constrained \
+                    or (r.async_pending and sr.start + sr.num_new_tokens >= r.num_tokens):
                 return True
         return False
 
@@ -204,6 +241,16 @@ class LLMEngine:
             return outs
         if self._pending is not None and self._needs_settled(so):
             outs += self.drain()
+            # the drain may have finished (EOS, a stop token, max_tokens) and freed requests
+            # that this step had already scheduled: they are neither planned nor run
+            so.decodes = [sr for sr in so.decodes if not sr.req.status.finished]
+            so.prefills = [sr for sr in so.prefills if not sr.req.status.finished]
+            self.last_step_empty = so.empty
+            self.last_num_tokens = so.num_tokens
+            if so.empty:
+                if not outs:
+                    self._flush_events()
+                return outs
         if self.offload is not None:
             self.offload.before_step(so)
         prev = self._pending[1] if self._pending is not None else None

@@ -187,6 +187,10 @@ class ModelRunner:
         self.casc_slots = 16                           # prefix partial slots per sequence
         self.cgraphs: dict[int, tuple] = {}
         self.lora = None  # engine/lora.py LoRAManager (set by the engine / TP follower)
+        # structured outputs: the token byte table (set by the engine) and the device arena of
+        # compiled grammars (created with the first guided request)
+        self.token_table = None
+        self.guided_arena = None
         self.kv = None
         self.num_blocks = 0
         # hybrid KV cache: windowed layers in their own pool (engine/hybrid_kv.py)
@@ -690,6 +694,32 @@ class ModelRunner:
             logits.index_copy_(0, rows, keep)
         return logits
 
+    def guided_acquire(self, grammar) -> None:
+        """Upload (once per engine) and pin a request's grammar; ValueError when it cannot fit."""
+        if self.guided_arena is None:
+            from llmd_amd.guided.arena import GuidedArena
+
+            self.guided_arena = GuidedArena(self.device, self.cfg.guided_arena_states)
+        self.guided_arena.acquire(grammar)
+
+    def guided_release(self, grammar) -> None:
+        if self.guided_arena is not None:
+            self.guided_arena.release(grammar)
+
+    def _guided_mask(self, logits, reqs):
+        """-inf over the tokens that the constrained rows' grammars forbid in their current
+        states (ops.guided_mask, in place); unconstrained rows are not touched."""
+        ar = self.guided_arena
+        off, n, st = [], [], []
+        for r in reqs:
+            g = r.params.guided
+            o, k = ar.lookup(g) if g is not None else (0, 0)
+            off.append(o)
+            n.append(k)
+            st.append(r.guided_state if g is not None else -1)
+        tb, to = self.token_table.on_device(self.device)
+        return ops.guided_mask(logits, ar.trans, ar.accept, off, n, st, tb, to, self.mc.eos_ids)
+
     def _sample(self, logits, reqs):
         ids, lp, top = self._sample_dev(logits, reqs)
         return self._to_host(ids, lp, reqs, top)
@@ -710,6 +740,8 @@ class ModelRunner:
         dev = self.device
         if any(r.params.penalized for r in reqs):
             logits = self._penalize(logits, reqs)
+        if any(r.params.constrained for r in reqs):
+            logits = self._guided_mask(logits, reqs)
         if any_k or any_p:
             logits = logits.float()
             ops.topk_topp_mask(logits, torch.from_numpy(topk).to(dev) if any_k else None,

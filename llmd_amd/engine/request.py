@@ -28,6 +28,11 @@ class SamplingParams:
     min_p: float = 0.0                 # drop tokens with prob < min_p x max prob
     logit_bias: Optional[dict] = None  # token id -> additive bias
     top_logprobs: int = 0              # OpenAI: the N most likely alternatives of every output token (<= 20)
+    guided: Any = None                 # structured outputs: a compiled llmd_amd.guided.Grammar, or None
+
+    @property
+    def constrained(self) -> bool:
+        return self.guided is not None
 
     @property
     def penalized(self) -> bool:
@@ -60,7 +65,10 @@ class SamplingParams:
             lp = 1
         elif lp is not None and not isinstance(lp, bool):
             top = lp
+        from llmd_amd import guided as _guided
+
         sp = cls(
+            guided=_guided.from_request(body),
             max_tokens=int(mt) if mt is not None else default_max,
             temperature=float(body.get("temperature", 1.0) if body.get("temperature") is not None else 1.0),
             top_p=float(g("top_p", 1.0)),
@@ -93,6 +101,9 @@ class SamplingParams:
             raise ValueError(f"min_p must be in [0, 1], got {self.min_p}")
         if not 0 <= self.top_logprobs <= 20:
             raise ValueError(f"top_logprobs must be in [0, 20], got {self.top_logprobs}")
+        if self.constrained and self.ignore_eos:
+            raise ValueError("ignore_eos cannot be combined with a guided-decoding constraint: "
+                             "the grammar decides when EOS is legal")
         if not 1 <= self.n <= 128:
             raise ValueError(f"n must be in [1, 128], got {self.n}")
         if self.max_tokens < 0 or self.temperature < 0 or not 0.0 < self.top_p <= 1.0:
@@ -173,6 +184,9 @@ class Request:
     # per output token: None, or the params.top_logprobs most likely (token id, logprob) pairs
     # (fewer when the row had fewer unmasked entries)
     output_top_logprobs: list = field(default_factory=list)
+    # structured outputs: the DFA state of params.guided after the output tokens so far (1 = start);
+    # it moves only where a real token is written, never on an async placeholder
+    guided_state: int = 1
 
     @property
     def cache_extra(self) -> int:

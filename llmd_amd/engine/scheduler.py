@@ -143,6 +143,10 @@ class Scheduler:
         self.errored: list[Request] = []  # finished by the scheduler itself (not via update)
         self._window_release = hasattr(block_manager, "after_compute")
         self._tok_arrays: dict[str, np.ndarray] = {}
+        # structured outputs (set by the engine): llmd_amd.guided.TokenTable, and a callback for
+        # a finished constrained request (its grammar is no longer pinned in the device arena)
+        self.token_table = None
+        self.on_guided_finish = None
 
     # ------------------------------------------------------------ admission
     def add_request(self, req: Request):
@@ -450,6 +454,7 @@ class Scheduler:
                 r.output_token_ids.append(tok)
                 r.output_logprobs.append(lp)
                 r.output_top_logprobs.append(rest[0] if rest else None)
+                self._guided_advance(r, tok)
                 if r.first_token_time is None:
                     r.first_token_time = now
                 r.last_token_time = now
@@ -507,12 +512,20 @@ class Scheduler:
                 r.output_logprobs[-1] = lp
                 r.output_top_logprobs[-1] = rest[0] if rest else None
                 r.async_pending = False
+                self._guided_advance(r, tok)
                 if r.first_token_time is None:
                     r.first_token_time = now
                 r.last_token_time = now
                 self._check_stop(r)
                 touched.append(r)
         return touched
+
+    def _guided_advance(self, r: Request, tok: int):
+        """A real token was written: the request's DFA state follows its bytes. EOS and other
+        length-0 tokens leave it where it is."""
+        g = r.params.guided
+        if g is not None:
+            r.guided_state = g.advance(r.guided_state, self.token_table.token(tok))
 
     def _check_stop(self, r: Request):
         p = r.params
@@ -539,6 +552,8 @@ class Scheduler:
     def _finish(self, r: Request, status: Status, free_blocks: bool = True):
         r.status = status
         r.finished_time = time.monotonic()
+        if r.params.guided is not None and self.on_guided_finish is not None:
+            self.on_guided_finish(r)
         ktp = r.kv_transfer_params or {}
         if ktp.get("do_remote_decode") and self.connector is not None and status != Status.FINISHED_ABORTED:
             # P side: keep blocks for the remote reader; the connector frees them

@@ -993,6 +993,44 @@ def top_logprobs(logits, n_per_row):
     return ids, lp
 
 
+def guided_mask(logits, trans, accept, dfa_off, dfa_n, state, tok_bytes, tok_off, eos_ids):
+    """Structured outputs: -inf, in place, over every token that the row's grammar forbids.
+
+    ``trans`` uint16 ``[cap, 256]`` / ``accept`` uint8 ``[cap]``: the arena of concatenated
+    byte-level DFAs (llmd_amd.guided) on the logits' device; ``tok_bytes`` uint8 /
+    ``tok_off`` int32 ``[V + 1]``: the token byte table there. ``dfa_off`` / ``dfa_n`` /
+    ``state``: HOST int sequences ``[B]`` - arena row of the grammar's state 0, its number of
+    states, and the row's local state (-1: an unconstrained row, never touched). They are
+    validated here, before upload, so that no out-of-range index reaches the device.
+    A token is kept when it has length > 0 and its bytes never reach state 0; the EOS ids are
+    kept exactly when the state is accepting. logits: bf16 or fp32, rows 16-byte aligned."""
+    import numpy as np
+
+    B, V = logits.shape
+    off = np.asarray(dfa_off, dtype=np.int64).reshape(-1)
+    n = np.asarray(dfa_n, dtype=np.int64).reshape(-1)
+    st = np.asarray(state, dtype=np.int64).reshape(-1)
+    if not (off.size == n.size == st.size == B):
+        raise ValueError("guided_mask: dfa_off, dfa_n and state need one entry per row")
+    cap = int(trans.shape[0])
+    on = st >= 0
+    if (st < -1).any() or (off[on] < 0).any() or (n[on] < 2).any() or (off[on] + n[on] > cap).any() \
+            or (st[on] >= n[on]).any():
+        raise ValueError("guided_mask: a row's grammar or state lies outside the DFA arena")
+    eos = [int(e) for e in eos_ids]
+    if any(not 0 <= e < V for e in eos):
+        raise ValueError("guided_mask: EOS id outside the vocabulary")
+    if not on.any():
+        return logits
+    off, n = np.where(on, off, 0), np.where(on, n, 0)
+    if not _gpu(logits):
+        return ref.guided_mask(logits, trans, accept, off, n, st, tok_bytes, tok_off, eos)
+    dev = logits.device
+    rows = torch.from_numpy(np.stack([off, n, st]).astype(np.int32)).to(dev, non_blocking=True)
+    native().guided_mask(logits, trans, accept, rows[0], rows[1], rows[2], tok_bytes, tok_off, eos)
+    return logits
+
+
 rope_cos_sin = ref.rope_cos_sin
 
 

@@ -390,3 +390,52 @@ def lora_bgmv(y, x, A, B, slot):
         d = torch.einsum("tr,tor->to", xa, B[s[on]].float())
         y[on] = (y[on].float() + d).to(y.dtype)
     return y
+
+
+def guided_allowed(trans, accept, off, n, state, tok_bytes, tok_off, V, eos_ids):
+    """bool [V]: the tokens a row in local ``state`` of the grammar at arena rows
+    [off, off + n) may emit (numpy; all tokens step together, byte position by byte position)."""
+    import numpy as np
+
+    trans, accept = np.asarray(trans), np.asarray(accept)
+    tok_bytes, tok_off = np.asarray(tok_bytes), np.asarray(tok_off)[: V + 1].astype(np.int64)
+    lens = np.diff(tok_off)
+    cur = np.full(V, state, dtype=np.int64)
+    cur[lens == 0] = 0
+    alive = np.flatnonzero(lens > 0)
+    j = 0
+    while alive.size:
+        b = tok_bytes[tok_off[alive] + j]
+        nxt = trans[off + cur[alive], b].astype(np.int64)
+        nxt[nxt >= n] = 0
+        cur[alive] = nxt
+        j += 1
+        alive = alive[(nxt != 0) & (lens[alive] > j)]
+    keep = cur != 0
+    for e in eos_ids:
+        keep[e] = bool(accept[off + state])
+    return keep
+
+
+def guided_mask(logits, trans, accept, dfa_off, dfa_n, state, tok_bytes, tok_off, eos_ids):
+    """Oracle of ops.guided_mask (csrc/ops/guided.hip): in place, -inf over the tokens the row's
+    grammar forbids; rows with state -1 untouched. ``trans`` / ``accept`` / token table: CPU
+    tensors or numpy arrays; ``dfa_off`` / ``dfa_n`` / ``state``: host sequences."""
+    import numpy as np
+
+    def host(a):
+        return a.numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+
+    trans, accept, tok_bytes, tok_off = host(trans), host(accept), host(tok_bytes), host(tok_off)
+    V = logits.shape[1]
+    memo = {}
+    for r in range(logits.shape[0]):
+        s = int(state[r])
+        if s < 0:
+            continue
+        key = (int(dfa_off[r]), int(dfa_n[r]), s)
+        if key not in memo:
+            memo[key] = torch.from_numpy(~guided_allowed(trans, accept, key[0], key[1], s, tok_bytes, tok_off, V,
+                                                         eos_ids))
+        logits[r].masked_fill_(memo[key].to(logits.device), float("-inf"))
+    return logits

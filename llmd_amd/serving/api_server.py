@@ -76,6 +76,7 @@ class OpenAIServer:
         mc = cfg.model_config
         self.tok = tokenizer or load_tokenizer(cfg.tokenizer, mc.vocab_size, mc.bos_token_id, mc.eos_ids[0])
         self._vocab = mc.vocab_size
+        self._guided_ready = None  # None: not tried; True; or why this tokenizer cannot serve guided requests
         self.lora = lora_manager
         self.opts = opts or ServingOptions()
         self.template = ChatTemplate(style_for(mc.model_type), model_dir=cfg.tokenizer,
@@ -292,6 +293,31 @@ class OpenAIServer:
                             for t, lp, alts in zip(toks, lps, tops)]}
 
     # ------------------------------------------------------------ completions
+    async def _guided_prepare(self, body) -> None:
+        """Structured outputs (guided_choice / guided_regex / guided_json / structured_outputs /
+        response_format json_schema): hand the engine the tokenizer's byte table on the first
+        such request, and compile the grammar off the event loop; SamplingParams.from_openai
+        then finds it in the compile cache. ValueError -> HTTP 400."""
+        from llmd_amd import guided
+
+        if guided.constraint_of(body) is None:
+            return
+        if body.get("ignore_eos"):
+            raise ValueError("ignore_eos cannot be combined with a guided-decoding constraint")
+        loop = asyncio.get_running_loop()
+        if self._guided_ready is None:
+            def table():
+                try:
+                    t = guided.TokenTable(*self.tok.token_bytes(self._vocab))
+                    self.aeng.engine.set_token_table(t)
+                    return True
+                except (ValueError, AttributeError) as e:
+                    return str(e) or "this tokenizer cannot serve guided requests"
+            self._guided_ready = await loop.run_in_executor(None, table)
+        if self._guided_ready is not True:
+            raise ValueError(self._guided_ready)
+        await loop.run_in_executor(None, guided.from_request, body)
+
     async def completions(self, req: web.Request):
         return await self._serve(req, chat=False)
 
@@ -325,6 +351,7 @@ class OpenAIServer:
             else:
                 prompts = [self._chat_ids(body)] if chat else self._prompt_ids(body)
             tools_on = chat and self._tools_active(body)
+            await self._guided_prepare(body)
             params = SamplingParams.from_openai(body, default_max=16 if not chat else
                                                 max(1, self.cfg.sched.max_model_len - 1), vocab_size=self._vocab)
         except (ValueError, TypeError) as e:
