@@ -73,7 +73,7 @@ int llmd_mgemm_add_rmsnorm(const void*, int64_t, const void*, int64_t, int, int,
 int llmd_mgemm_silu(const void*, int64_t, const void*, int64_t, int, int, int, int, int, void*, int64_t, hipStream_t);
 int llmd_pgemm(const void*, int64_t, const void*, int64_t, void*, int64_t, int, int, int, int, int, void*,
                hipStream_t);
-int64_t llmd_pgemm_ws_bytes(int, int, int, int, int);
+int64_t llmd_pgemm_ws_bytes(int, int, int, int);
 int llmd_pgemm_fp8(const void*, int64_t, const float*, const void*, int64_t, const float*, void*, int64_t, int, int,
                    int, int, void*, hipStream_t);
 int64_t llmd_pgemm_fp8_ws_bytes(int, int, int, int);
@@ -562,22 +562,23 @@ void mgemm_add_rmsnorm(torch::Tensor out, torch::Tensor x, torch::Tensor w, int6
 }
 
 // y [M, N] = x [M, K] . w [N, K]^T for prefill-sized M on the 256 x 256 LDS-DMA MFMA
-// GEMM (csrc/ops/pgemm.hip); epi 1 = fused SiLU-and-mul over gate/up columns interleaved
-// per 256-column tile, epi 3 = the same on the plain [gate; up] weight (variants 3-5); y is
-// then [M, N / 2]
-// variant 1 with split_k: a mostly idle last wave of tiles runs split over K into an fp32
+// GEMM (csrc/ops/pgemm.hip), variant 0 (8 waves), 3 (PGR2) or 6 (persistent PGR2); epi 3
+// (variants 3 and 6) = fused SiLU-and-mul on the plain [gate; up] weight, y is then [M, N / 2]
+// split_k (epi 0): a mostly idle last wave of tiles runs split over K into an fp32
 // workspace (allocated here from the caching allocator) and is reduced by a second kernel
 void pgemm(torch::Tensor y, torch::Tensor x, torch::Tensor w, int64_t epi, int64_t variant, bool split_k) {
   const c10::hip::OptionalHIPGuard device_guard(dev_of(y));
   CHECK_CUDA(x); CHECK_BF16(x); CHECK_BF16(w); CHECK_BF16(y); CHECK_INNER(x); CHECK_INNER(w); CHECK_INNER(y);
+  TORCH_CHECK(variant == 0 || variant == 3 || variant == 6, "pgemm: variant ", variant, " (0, 3 or 6)");
+  TORCH_CHECK(epi == 0 || epi == 3, "pgemm: epi ", epi, " (0, or 3 = SiLU on the [gate; up] weight)");
+  TORCH_CHECK(epi != 3 || variant != 0, "pgemm: epi 3 (SiLU on the [gate; up] weight) needs variant 3 or 6");
   TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && y.dim() == 2, "pgemm: 2-D operands");
   const int64_t M = x.size(0), K = x.size(1), N = w.size(0);
   TORCH_CHECK(w.size(1) == K && K % 64 == 0 && N % 256 == 0, "pgemm: N % 256 == 0, K % 64 == 0");
-  TORCH_CHECK(y.size(0) == M && y.size(1) == ((epi == 1 || epi == 3) ? N / 2 : N), "pgemm: output shape");
-  TORCH_CHECK(epi != 3 || (variant >= 3 && variant <= 6), "pgemm: epi 3 (SiLU on the [gate; up] weight) needs variant 3-6");
+  TORCH_CHECK(y.size(0) == M && y.size(1) == (epi == 3 ? N / 2 : N), "pgemm: output shape");
   TORCH_CHECK(x.stride(0) % 8 == 0 && w.stride(0) % 8 == 0 && y.stride(0) % 8 == 0, "pgemm: 16-B row alignment");
   torch::Tensor ws;
-  const int64_t wsb = split_k ? llmd_pgemm_ws_bytes((int)M, (int)N, (int)K, (int)epi, (int)variant) : 0;
+  const int64_t wsb = split_k ? llmd_pgemm_ws_bytes((int)M, (int)N, (int)K, (int)epi) : 0;
   if (wsb > 0) ws = torch::empty({wsb / 4}, x.options().dtype(torch::kFloat));
   int rc = llmd_pgemm(x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), y.data_ptr(), y.stride(0), (int)M,
                       (int)N, (int)K, (int)epi, (int)variant, wsb > 0 ? ws.data_ptr() : nullptr, cur_stream());

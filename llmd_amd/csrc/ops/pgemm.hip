@@ -2,7 +2,15 @@
 // QKV / O / gate-up / down projections of a prefill chunk (the
 // hipBLASLt Cijk_* kernels that take ~68 % of the 70B serving bench).
 //
-// CDNA4 design (one 256 x 256 output tile per 512-thread workgroup, 1 per CU):
+// Three kernels, the ones the dispatch table (ops/pgemm_table.py) names, all on 256 x 256
+// output tiles, one workgroup per CU, operands by LDS-DMA:
+//   variant 0  pgemm_kernel   8 waves, staggered 4-phase K-step (described here);
+//   variant 3  pgemm6_kernel  "PGR2": 4 waves, the K-step's fragments in registers (below);
+//   variant 6  pgemm7_kernel  persistent PGR2 (below); its split-K tail is pgemm6_kernel.
+// Variants 0 and 3 have the plain epilogue (EPI_NONE) and the fp32 split-K partial (EPI_F32),
+// variants 3 and 6 also the fused SiLU-and-mul on the [gate; up] weight (EPI_SILU_STD).
+//
+// Variant 0 (one 256 x 256 output tile per 512-thread workgroup, 1 per CU):
 //   * 8 waves as 2 (M) x 4 (N); a wave owns 128 x 64 of C, as four 64 x 32
 //     quadrants of 4 x 2 mfma_f32_16x16x32_bf16 tiles (128 accumulator regs);
 //   * K-steps of 64 through TWO LDS buffers of 64 KB (A 256 x 128 B, W 256 x
@@ -25,9 +33,6 @@
 //   * epilogue through the (then free) LDS: C is computed transposed (W frags
 //     as the MFMA's first operand) so each lane holds 4 consecutive columns,
 //     written as 8-B LDS stores, read back as 16-B rows and stored coalesced.
-//     EPI_SILU: gate/up columns interleaved per 256-column tile (128 gate then
-//     128 up, ops.pgemm_pack_gate_up) -> silu(g) * u is stored directly as the
-//     [M, N/2] activation (no separate act kernel, no [M, N] round trip).
 //
 // Requirements (checked by the host wrapper): N % 256 == 0, K % 64 == 0,
 // 16-B aligned rows; any M (rows past M are clamped on load, not stored).
@@ -46,10 +51,12 @@ constexpr int BUF = 4 * HALF;       // one K-step: A q0, A q1, W q0, W q1
 constexpr int LDS_BYTES = 2 * BUF;  // 128 KB
 constexpr int GROUP_M = 8;
 
-// EPI_SILU_STD (variants 3-5 only): the fused SiLU-and-mul on the model's own [gate; up] weight
-// ([2F, K], F % 128 == 0): tile tn's W rows are gate rows [128 tn, +128) then up rows
-// [F + 128 tn, +128) - the same tile image as EPI_SILU on a packed weight, no repacking.
-enum { EPI_NONE = 0, EPI_SILU = 1, EPI_F32 = 2, EPI_SILU_STD = 3 };
+// EPI_SILU_STD (variants 3 and 6 only): the fused SiLU-and-mul on the model's own [gate; up]
+// weight ([2F, K], F % 128 == 0): tile tn's W rows are gate rows [128 tn, +128) then up rows
+// [F + 128 tn, +128), so tile columns [0, 128) are gate, [128, 256) the matching up, and
+// silu(g) * u is stored directly as the [M, F] activation (no act kernel, no [M, 2F] round
+// trip). The values are the binding's contract (1 was a pre-packed gate/up layout, removed).
+enum { EPI_NONE = 0, EPI_F32 = 2, EPI_SILU_STD = 3 };
 
 __device__ __forceinline__ void dma16(const void* src, char* lds) {
   __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)src,
@@ -83,7 +90,7 @@ __device__ __forceinline__ void tile_mn(int L, int tiles_m, int tiles_n, int& tm
   tn = (L % per_group) / gm;
 }
 
-// Launch forms (host: llmd_pgemm, both variants): nsplit == 1 -> tiles [tile0, tile0 + grid)
+// Launch forms (host: llmd_pgemm; pgemm6_kernel takes the same): nsplit == 1 -> tiles [tile0, tile0 + grid)
 // over the whole K (data-parallel); nsplit > 1 (EPI_F32) -> the grid covers `tail` tiles from
 // tile0 x nsplit K-ranges, each block writing its fp32 partial tile to ws[split][tile][256][256]
 // (pgemm_splitk_reduce sums them). The tail split turns a last, mostly idle wave of tiles
@@ -316,474 +323,23 @@ __global__ __launch_bounds__(NT, 1) void pgemm_kernel(const uint16_t* __restrict
           *reinterpret_cast<u32x2_t*>(img + row * 128 + chunk * 16 + (col & 7) * 2) = p;
         }
   __syncthreads();
-  if constexpr (EPI == EPI_NONE) {
-    // each wave stores its own 128 x 64 block: 8 rows x 128 B per instruction
+  // each wave stores its own 128 x 64 block: 8 rows x 128 B per instruction
 #pragma unroll 4
-    for (int it = 0; it < 16; ++it) {
-      const int row = it * 8 + (lane >> 3), c = lane & 7;
-      const int m = m0 + wr * 128 + row;
-      const u32x4_t v = *reinterpret_cast<const u32x4_t*>(img + row * 128 + ((c ^ (row & 7)) * 16));
-      if (m < M) *reinterpret_cast<u32x4_t*>(C + (int64_t)m * ldc + n0 + wc * 64 + c * 8) = v;
-    }
-  } else {
-    // EPI_SILU: tile columns [0,128) gate, [128,256) up -> 128 output columns at n0 / 2.
-    // Waves wc = 0,1 hold gate cols [0,128), wc = 2,3 the matching up cols; the
-    // wc < 2 waves combine their image with the partner wave's (wc + 2) image.
-    if (wc < 2) {
-      const char* up = lds + (w + 2) * 16384;
-#pragma unroll 4
-      for (int it = 0; it < 16; ++it) {
-        const int row = it * 8 + (lane >> 3), c = lane & 7;
-        const int m = m0 + wr * 128 + row;
-        const int off = row * 128 + ((c ^ (row & 7)) * 16);
-        float gf[8], uf[8], of[8];
-        unpack8(*reinterpret_cast<const u32x4_t*>(img + off), gf);
-        unpack8(*reinterpret_cast<const u32x4_t*>(up + off), uf);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) of[e] = gf[e] / (1.f + __expf(-gf[e])) * uf[e];
-        if (m < M) *reinterpret_cast<u32x4_t*>(C + (int64_t)m * ldc + n0 / 2 + wc * 64 + c * 8) = pack8(of);
-      }
-    }
+  for (int it = 0; it < 16; ++it) {
+    const int row = it * 8 + (lane >> 3), c = lane & 7;
+    const int m = m0 + wr * 128 + row;
+    const u32x4_t v = *reinterpret_cast<const u32x4_t*>(img + row * 128 + ((c ^ (row & 7)) * 16));
+    if (m < M) *reinterpret_cast<u32x4_t*>(C + (int64_t)m * ldc + n0 + wc * 64 + c * 8) = v;
   }
 }
 
 // ---------------------------------------------------------------------------
-// Variant 4W: 4 waves (one per SIMD), each 128 x 128 of C (8 x 8 tiles of
-// mfma_f32_16x16x32_bf16: 256 accumulator registers, AGPR-resident), the form
-// hipBLASLt's fastest MT256x256x64 kernels take. With one wave per SIMD the
-// wave itself must keep its matrix pipe fed, so fragment reads are software-
-// pipelined one k-substep (32) ahead in a second register set, interleaved
-// 1 ds_read : 4 MFMA, and there are only two barriers per 64-deep K-step.
-// LDS: 4 slots of 32 KB, slot (kt & 1) * 2 + h holds k-half h (32 wide) of
-// K-step kt for A and W ([256 rows][64 B], 16-B chunks swizzled by
-// F[(row >> 2) & 3], conflict-free for the 16x16x32 operand reads). A slot is
-// refilled right after the barrier that follows its last fragment read, so
-// every half has three substeps (~3000 cycles) to land; counted vmcnt(16).
-constexpr int NT4 = 256;
-constexpr int SLOT4 = 32768;  // one k-half of A (16 KB) + of W (16 KB)
-
-// The 64 accumulators (256 registers) fill the accumulator file exactly; through the
-// builtin, hipcc's register allocator re-homes loop-carried accumulators every
-// iteration (~100-450 v_accvgpr moves per 64 MFMAs, with MFMA-result read stalls).
-// As an asm statement with the accumulator TIED in an AGPR ("+a") every tile stays
-// in place (0 moves). Hazards the compiler cannot see: an MFMA result read by a
-// non-MFMA instruction needs 12 wait states (8-pass XDL) -> mfma_drain() before the
-// epilogue; the A/B operands come straight from ds_read (lgkmcnt-ordered by hipcc,
-// which tracks the asm's "v" inputs), never from a VALU write in the 2 states before.
-__device__ __forceinline__ void mfma16_acc(f32x4_t& acc, const s16x8_t& a, const s16x8_t& b) {
-  asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b));
-}
-__device__ __forceinline__ void mfma_drain() { asm volatile("s_nop 7\n\ts_nop 7" ::: "memory"); }
-
-__device__ __forceinline__ int swz4(int row, int c) {
-  // F = {0, 2, 3, 1}: every ds_read_b128 lane group of a 16 x 4-chunk read hits 16 distinct slots
-  return c ^ ((0x1E >> (2 * ((row >> 2) & 3))) & 3);
-}
-
-// Same launch forms as pgemm_kernel (tile0 / nsplit / ws).
-template <int EPI>
-__global__ __launch_bounds__(NT4, 1) void pgemm4_kernel(const uint16_t* __restrict__ A, int64_t lda,
-                                                        const uint16_t* __restrict__ W, int64_t ldw,
-                                                        uint16_t* __restrict__ C, int64_t ldc, int M, int N, int K,
-                                                        int tile0, int nsplit, float* __restrict__ ws) {
-  __shared__ __attribute__((aligned(1024))) char lds[4 * SLOT4];  // the ONLY LDS object
-  const int tiles_m = (M + BM - 1) / BM, tiles_n = N / BN;
-  const int b = xcd_remap(blockIdx.x, gridDim.x);
-  const int tail = gridDim.x / nsplit;
-  const int t_local = b % tail, split = b / tail;
-  const int nk_all = K / BK;
-  const int chunk = (nk_all + nsplit - 1) / nsplit;
-  const int kbeg = split * chunk;
-  const int nk = min(chunk, nk_all - kbeg);
-  int tm, tn;
-  tile_mn(tile0 + t_local, tiles_m, tiles_n, tm, tn);
-  const int m0 = tm * BM, n0 = tn * BN;
-  A += (int64_t)kbeg * BK;
-  W += (int64_t)kbeg * BK;
-
-  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-  const int wr = w >> 1, wc = w & 1;
-
-  // DMA: a k-half of A is 256 rows x 64 B = 16 pieces of 1 KB (16 rows each); wave w moves
-  // pieces 4w..4w+3 of A and of W. Lane: row 16 * piece + (lane >> 2), slot lane & 3.
-  uint32_t aoff[4], woff[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int row = 16 * (4 * w + j) + (lane >> 2);
-    const int c = swz4(row, lane & 3);
-    aoff[j] = (uint32_t)(min(m0 + row, M - 1) * lda + c * 8);
-    woff[j] = (uint32_t)((n0 + row) * ldw + c * 8);
-  }
-  // half index q = 2 * kt + h, slot (kt & 1) * 2 + h = q & 3; a half is 8 LDS-DMA pieces per wave
-  // (A rows 0..3, W rows 4..7)
-  auto issue_piece = [&](int q, int p) {
-    char* dst = lds + (q & 3) * SLOT4 + (4 * w) * 1024;
-    const int k0 = (q >> 1) * BK + (q & 1) * 32;
-    if (p < 4) dma16(A + aoff[p] + k0, dst + p * 1024);
-    else dma16(W + woff[p - 4] + k0, dst + 16384 + (p - 4) * 1024);
-  };
-  auto issue = [&](int q) {
-#pragma unroll
-    for (int p = 0; p < 8; ++p) issue_piece(q, p);
-  };
-  const int nq = 2 * nk;
-
-  // fragment reads: tile row r = 16 * t + (lane & 15), chunk lane >> 4; (r >> 2) & 3 does not depend on t
-  const int fr = lane & 15, fq = lane >> 4;
-  const int rd = fr * 64 + swz4(fr, fq) * 16;
-  const int a_rd = (wr * 128) * 64 + rd, w_rd = 16384 + (wc * 128) * 64 + rd;
-
-  f32x4_t acc[8][8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-  s16x8_t fa0[8], fw0[8], fa1[8], fw1[8];
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_nop 4" ::: "memory");  // v_accvgpr_write (zero init) -> MFMA srcC
-  __builtin_amdgcn_sched_barrier(0);
-
-  // One substep = 64 MFMAs on (fa, fw), row i of 8 at a time. Around each row: the next
-  // substep's two fragment reads of row i (from `nxt` into na / nw) before it, and one of
-  // the 8 LDS-DMA pieces of half `dq` (the refill of the slot the PREVIOUS substep read)
-  // after it - DMA issue costs ~60-180 cycles each, so it must ride inside the MFMA stream,
-  // not stall the wave at the boundary.
-#define PG4_SUBSTEP(fa, fw, na, nw, nxt, dq)                                                               \
-  {                                                                                                        \
-    const char* nb_ = (nxt);                                                                               \
-    const bool dma_ = (dq) < nq;                                                                           \
-    _Pragma("unroll") for (int i = 0; i < 8; ++i) {                                                        \
-      na[i] = *reinterpret_cast<const s16x8_t*>(nb_ + a_rd + i * 1024);                                    \
-      nw[i] = *reinterpret_cast<const s16x8_t*>(nb_ + w_rd + i * 1024);                                    \
-      _Pragma("unroll") for (int j = 0; j < 8; ++j) mfma16_acc(acc[i][j], fw[j], fa[i]);                   \
-      if (dma_) issue_piece((dq), i);                                                                      \
-      __builtin_amdgcn_sched_barrier(0);                                                                   \
-    }                                                                                                      \
-  }
-  // boundary: this wave's fragment reads retired, the half read next has landed (every wave,
-  // after the barrier)
-  auto boundary = [&](int wait_q, int issued_hi) {
-    // lgkmcnt(0) as the builtin, so hipcc's waitcnt pass sees the fragment reads retired
-    // (after an asm wait it re-waits before the next substep's first MFMA)
-    __builtin_amdgcn_s_waitcnt(0xC07F);
-    const int younger = min(2, max(0, issued_hi - wait_q - 1));
-    if (younger >= 2) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-    else if (younger == 1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    bar();
-  };
-
-  // prologue: halves 0..3 (K-steps 0, 1); read K-step 0 half 0 fragments
-#pragma unroll
-  for (int q = 0; q < 4; ++q)
-    if (q < nq) issue(q);
-  {
-    const int hi = min(4, nq);
-    const int younger = hi - 1;  // wait for half 0
-    if (younger >= 3) asm volatile("s_waitcnt vmcnt(24)" ::: "memory");
-    else if (younger == 1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    bar();
-  }
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    fa0[i] = *reinterpret_cast<const s16x8_t*>(lds + a_rd + i * 1024);
-    fw0[i] = *reinterpret_cast<const s16x8_t*>(lds + w_rd + i * 1024);
-  }
-  // before half 1 of K-step 0 is read (during substep (0, 0)) it must have landed
-  {
-    const int hi = min(4, nq);
-    const int younger = hi - 2;
-    if (younger >= 2) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_waitcnt(0xC07F);  // the prologue fragments, visibly to hipcc (else it re-waits in the loop)
-    bar();
-  }
-  int issued = min(4, nq);
-  // Substep u = 2 kt + s computes half u, reads half u + 1 and refills with half u + 4 the
-  // slot of half u (read by substep u - 1, retired by the boundary before u). Every K-step
-  // in one loop body (a peeled last step makes hipcc re-home the accumulators): the last
-  // step's read-ahead of the nonexistent next half reads a stale slot into registers nothing
-  // consumes, its waits drain to 0.
-  for (int kt = 0; kt < nk; ++kt) {
-    const int q0 = 2 * kt;
-    PG4_SUBSTEP(fa0, fw0, fa1, fw1, lds + ((q0 + 1) & 3) * SLOT4, q0 + 4);
-    if (q0 + 4 < nq) issued = q0 + 5;
-    boundary(q0 + 2, issued);
-    PG4_SUBSTEP(fa1, fw1, fa0, fw0, lds + ((q0 + 2) & 3) * SLOT4, q0 + 5);
-    if (q0 + 5 < nq) issued = q0 + 6;
-    boundary(q0 + 3, issued);
-  }
-#undef PG4_SUBSTEP
-  mfma_drain();  // the last MFMA results before the epilogue reads them (asm MFMAs are opaque to hipcc)
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-  if constexpr (EPI == EPI_F32) {
-    // fp32 partial tile, row-major [256][256]: 4 consecutive columns per lane -> 16-B stores
-    float* wt = ws + ((int64_t)split * tail + t_local) * (BM * BN);
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int row = wr * 128 + 16 * i + fr, col = wc * 128 + 16 * j + 4 * fq;
-        *reinterpret_cast<f32x4_t*>(wt + row * BN + col) = acc[i][j];
-      }
-    return;
-  }
-  __syncthreads();
-
-  // epilogue: acc[i][j][r] = C[m][n], m = wr*128 + 16 i + (lane & 15), n = wc*128 + 16 j + 4 (lane >> 4) + r.
-  // wave image: [128 rows][128 cols] bf16 (256-B rows), 16-B chunks XOR-swizzled by row & 15
-  char* img = lds + w * 32768;
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int row = 16 * i + fr, col = 16 * j + 4 * fq;
-      const f32x4_t v = acc[i][j];
-      u32x2_t p;
-      p[0] = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);
-      p[1] = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
-      *reinterpret_cast<u32x2_t*>(img + row * 256 + (((col >> 3) ^ (row & 15)) * 16) + (col & 7) * 2) = p;
-    }
-  __syncthreads();
-  if constexpr (EPI == EPI_NONE) {
-#pragma unroll 4
-    for (int it = 0; it < 32; ++it) {
-      const int row = it * 4 + (lane >> 4), c = lane & 15;
-      const int m = m0 + wr * 128 + row;
-      const u32x4_t v = *reinterpret_cast<const u32x4_t*>(img + row * 256 + ((c ^ (row & 15)) * 16));
-      if (m < M) *reinterpret_cast<u32x4_t*>(C + (int64_t)m * ldc + n0 + wc * 128 + c * 8) = v;
-    }
-  } else {
-    // gate = tile columns [0, 128) (waves wc = 0), up = [128, 256) (wc = 1): wave (wr, 0) combines
-    if (wc == 0) {
-      const char* up = lds + (w + 1) * 32768;
-#pragma unroll 4
-      for (int it = 0; it < 32; ++it) {
-        const int row = it * 4 + (lane >> 4), c = lane & 15;
-        const int m = m0 + wr * 128 + row;
-        const int off = row * 256 + ((c ^ (row & 15)) * 16);
-        float gf[8], uf[8], of[8];
-        unpack8(*reinterpret_cast<const u32x4_t*>(img + off), gf);
-        unpack8(*reinterpret_cast<const u32x4_t*>(up + off), uf);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) of[e] = gf[e] / (1.f + __expf(-gf[e])) * uf[e];
-        if (m < M) *reinterpret_cast<u32x4_t*>(C + (int64_t)m * ldc + n0 / 2 + c * 8) = pack8(of);
-      }
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------
-// Variant 2 ("RS4"): the 4-wave / 128 x 128-per-wave form of variant 1, but the
-// operands are REGISTER-staged (global_load_dwordx4 -> VGPR -> ds_write_b128)
-// instead of LDS-DMA. Why: with one wave per SIMD there is no partner wave to
-// hide an instruction's issue cost behind, and an LDS-DMA piece costs ~60-180
-// cycles of issue among MFMAs (MI355X_MICROARCH.md, LDS-DMA piece row) - 8 per
-// 64 MFMA (1024 cycles) in variant 1 - while a global_load / ds_write issues in
-// a few cycles. One wave per SIMD has 512 registers (256 AGPR accumulators +
-// 256 VGPR), so the staging ring that would not fit at two waves per SIMD fits.
-//
-// Per 64-deep K-step kt (LDS buffer cur = kt & 1, 2 x 64 KB):
-//   substep 0: 64 MFMA on fragment set 0 (k 0..31); between MFMA rows: the 16
-//              fragment reads of set 1 (k 32..63) from buf cur and the 16
-//              ds_write_b128 of step kt+1's staged tile into buf cur ^ 1;
-//   lgkmcnt(0) + s_barrier (the ONE barrier per K-step);
-//   substep 1: 64 MFMA on set 1; between rows: the 16 fragment reads of step
-//              kt+1's set 0 from buf cur ^ 1 and the 16 global loads of step
-//              kt+2 into the staging registers.
-// Buffer cur ^ 1 was last read in step kt-1's substep 0, before step kt-1's
-// barrier, so substep 0 of kt may overwrite it; it is read again only after
-// step kt's barrier. W fragments are read before A fragments in each set (every
-// MFMA row needs all 8 W fragments). LDS image: [256 rows][64 k] bf16 per
-// operand, 16-B chunk c of row r at chunk c ^ ((r >> 1) & 7): conflict-free for
-// the ds_read_b128 lane groups of the 16 x 16 x 32 operand reads and for the
-// 8-lane ds_write_b128 groups (one 128-B row each).
-constexpr int NT5 = 256;
-constexpr int OPB5 = BM * BK * 2;  // one operand of one K-step: 32 KB
-constexpr int BUF5 = 2 * OPB5;     // A + W
-
-__device__ __forceinline__ int swz5(int row, int c) { return c ^ ((row >> 1) & 7); }
-
-template <int EPI>
-__global__ __launch_bounds__(NT5, 1) void pgemm5_kernel(const uint16_t* __restrict__ A, int64_t lda,
-                                                        const uint16_t* __restrict__ W, int64_t ldw,
-                                                        uint16_t* __restrict__ C, int64_t ldc, int M, int N, int K,
-                                                        int tile0, int nsplit, float* __restrict__ ws) {
-  __shared__ __attribute__((aligned(1024))) char lds[2 * BUF5];  // the ONLY LDS object
-  const int tiles_m = (M + BM - 1) / BM, tiles_n = N / BN;
-  const int b = xcd_remap(blockIdx.x, gridDim.x);
-  const int tail = gridDim.x / nsplit;
-  const int t_local = b % tail, split = b / tail;
-  const int nk_all = K / BK;
-  const int chunk = (nk_all + nsplit - 1) / nsplit;
-  const int kbeg = split * chunk;
-  const int nk = min(chunk, nk_all - kbeg);
-  int tm, tn;
-  tile_mn(tile0 + t_local, tiles_m, tiles_n, tm, tn);
-  const int m0 = tm * BM, n0 = tn * BN;
-  A += (int64_t)kbeg * BK;
-  W += (int64_t)kbeg * BK;
-
-  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-  const int wr = w >> 1, wc = w & 1;
-
-  // staging: load i (0..7) of an operand = row 32 i + (tid >> 3), chunk tid & 7
-  const int srow = tid >> 3, sc = tid & 7;
-  uint32_t aoff[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) aoff[i] = (uint32_t)(min(m0 + 32 * i + srow, M - 1) * lda + sc * 8);
-  const uint32_t woff0 = (uint32_t)((n0 + srow) * ldw + sc * 8);
-  const uint32_t wstep = (uint32_t)(32 * ldw);
-  // LDS byte offset of this thread's chunk in row 32 i + srow ((32 i + srow) >> 1 & 7 == (srow >> 1) & 7)
-  const int st_off = srow * 128 + swz5(srow, sc) * 16;
-
-  // fragment reads: row 16 t + (lane & 15), chunk 4 s + (lane >> 4)
-  const int fr = lane & 15, fq = lane >> 4;
-  const int rd0 = fr * 128 + swz5(fr, fq) * 16, rd1 = fr * 128 + swz5(fr, 4 + fq) * 16;
-  const int a_rd = (wr * 128) * 128, w_rd = OPB5 + (wc * 128) * 128;
-
-  f32x4_t acc[8][8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-  s16x8_t fa0[8], fw0[8], fa1[8], fw1[8];
-  u32x4_t ga[8], gw[8];
-
-  auto gload = [&](int kt, int i) {  // loads i of A and of W, K-step kt
-    const int k0 = min(kt, nk - 1) * BK;
-    ga[i] = *reinterpret_cast<const u32x4_t*>(A + aoff[i] + k0);
-    gw[i] = *reinterpret_cast<const u32x4_t*>(W + woff0 + i * wstep + k0);
-  };
-  auto swrite = [&](char* buf, int i) {
-    *reinterpret_cast<u32x4_t*>(buf + i * 4096 + st_off) = ga[i];
-    *reinterpret_cast<u32x4_t*>(buf + OPB5 + i * 4096 + st_off) = gw[i];
-  };
-
-  // prologue: step 0 -> buf 0, step 1 -> staging, set 0 of step 0 -> registers
-#pragma unroll
-  for (int i = 0; i < 8; ++i) gload(0, i);
-#pragma unroll
-  for (int i = 0; i < 8; ++i) swrite(lds, i);
-#pragma unroll
-  for (int i = 0; i < 8; ++i) gload(1, i);
-  __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): this wave's ds_writes done
-  bar();
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    fw0[i] = *reinterpret_cast<const s16x8_t*>(lds + w_rd + i * 2048 + rd0);
-    fa0[i] = *reinterpret_cast<const s16x8_t*>(lds + a_rd + i * 2048 + rd0);
-  }
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_nop 4" ::: "memory");  // v_accvgpr_write (zero init) -> MFMA srcC
-  __builtin_amdgcn_sched_barrier(0);
-
-  // one MFMA row i (8 MFMA on acc[i][*]) with two "side" instructions after it
-#define PG5_ROW(fa, fw, i, SIDE)                                                       \
-  {                                                                                    \
-    _Pragma("unroll") for (int j = 0; j < 8; ++j) mfma16_acc(acc[i][j], fw[j], fa[i]); \
-    SIDE;                                                                              \
-    __builtin_amdgcn_sched_barrier(0);                                                 \
-  }
-  for (int kt = 0; kt < nk; ++kt) {
-    char* cur = lds + (kt & 1) * BUF5;
-    char* nxt = lds + ((kt & 1) ^ 1) * BUF5;
-    // substep 0: set 0; read set 1 (W first) from cur, write step kt+1 into nxt
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      PG5_ROW(fa0, fw0, i, {
-        if (i < 4) {
-          fw1[2 * i] = *reinterpret_cast<const s16x8_t*>(cur + w_rd + (2 * i) * 2048 + rd1);
-          fw1[2 * i + 1] = *reinterpret_cast<const s16x8_t*>(cur + w_rd + (2 * i + 1) * 2048 + rd1);
-        } else {
-          fa1[2 * i - 8] = *reinterpret_cast<const s16x8_t*>(cur + a_rd + (2 * i - 8) * 2048 + rd1);
-          fa1[2 * i - 7] = *reinterpret_cast<const s16x8_t*>(cur + a_rd + (2 * i - 7) * 2048 + rd1);
-        }
-        swrite(nxt, i);
-      });
-    }
-    __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): set-1 reads and the nxt writes retired
-    bar();
-    // substep 1: set 1; read step kt+1's set 0 (W first) from nxt, load step kt+2
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      PG5_ROW(fa1, fw1, i, {
-        if (i < 4) {
-          fw0[2 * i] = *reinterpret_cast<const s16x8_t*>(nxt + w_rd + (2 * i) * 2048 + rd0);
-          fw0[2 * i + 1] = *reinterpret_cast<const s16x8_t*>(nxt + w_rd + (2 * i + 1) * 2048 + rd0);
-        } else {
-          fa0[2 * i - 8] = *reinterpret_cast<const s16x8_t*>(nxt + a_rd + (2 * i - 8) * 2048 + rd0);
-          fa0[2 * i - 7] = *reinterpret_cast<const s16x8_t*>(nxt + a_rd + (2 * i - 7) * 2048 + rd0);
-        }
-        gload(kt + 2, i);
-      });
-    }
-  }
-#undef PG5_ROW
-  mfma_drain();
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-  if constexpr (EPI == EPI_F32) {
-    float* wt = ws + ((int64_t)split * tail + t_local) * (BM * BN);
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int row = wr * 128 + 16 * i + fr, col = wc * 128 + 16 * j + 4 * fq;
-        *reinterpret_cast<f32x4_t*>(wt + row * BN + col) = acc[i][j];
-      }
-    return;
-  }
-  __syncthreads();
-  // epilogue (as variant 1): acc[i][j][r] = C[m][n], m = wr*128 + 16 i + (lane & 15),
-  // n = wc*128 + 16 j + 4 (lane >> 4) + r; per-wave [128][128] bf16 image, chunks XOR row & 15
-  char* img = lds + w * 32768;
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int row = 16 * i + fr, col = 16 * j + 4 * fq;
-      const f32x4_t v = acc[i][j];
-      u32x2_t p;
-      p[0] = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);
-      p[1] = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
-      *reinterpret_cast<u32x2_t*>(img + row * 256 + (((col >> 3) ^ (row & 15)) * 16) + (col & 7) * 2) = p;
-    }
-  __syncthreads();
-  if constexpr (EPI == EPI_NONE) {
-#pragma unroll 4
-    for (int it = 0; it < 32; ++it) {
-      const int row = it * 4 + (lane >> 4), c = lane & 15;
-      const int m = m0 + wr * 128 + row;
-      const u32x4_t v = *reinterpret_cast<const u32x4_t*>(img + row * 256 + ((c ^ (row & 15)) * 16));
-      if (m < M) *reinterpret_cast<u32x4_t*>(C + (int64_t)m * ldc + n0 + wc * 128 + c * 8) = v;
-    }
-  } else {
-    // gate = tile columns [0, 128) (waves wc = 0), up = [128, 256) (wc = 1): both waves of a row
-    // half store 64 rows each of silu(g) * u
-    const char* gimg = lds + (wr * 2) * 32768;
-    const char* uimg = gimg + 32768;
-#pragma unroll 4
-    for (int it = 0; it < 16; ++it) {
-      const int row = wc * 64 + it * 4 + (lane >> 4), c = lane & 15;
-      const int m = m0 + wr * 128 + row;
-      const int off = row * 256 + ((c ^ (row & 15)) * 16);
-      float gf[8], uf[8], of[8];
-      unpack8(*reinterpret_cast<const u32x4_t*>(gimg + off), gf);
-      unpack8(*reinterpret_cast<const u32x4_t*>(uimg + off), uf);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) of[e] = gf[e] / (1.f + __expf(-gf[e])) * uf[e];
-      if (m < M) *reinterpret_cast<u32x4_t*>(C + (int64_t)m * ldc + n0 / 2 + c * 8) = pack8(of);
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------
-// Variant 3 ("PGR2"): 4 waves x (128 x 128 of C) as variant 1, restructured so
-// that each 64-deep K-step's fragments (both 32-deep halves, 32 ds_read_b128 =
-// 128 VGPR) are read into registers BEFORE its LDS buffer is refilled. With the
+// Variant 3 ("PGR2"): 4 waves (one per SIMD), each 128 x 128 of C (8 x 8 tiles
+// of mfma_f32_16x16x32_bf16: 256 accumulator registers, AGPR-resident), the
+// form hipBLASLt's fastest MT256x256x64 kernels take. With one wave per SIMD
+// the wave itself must keep its matrix pipe fed, so each 64-deep K-step's
+// fragments (both 32-deep halves, 32 ds_read_b128 = 128 VGPR) are read into
+// registers BEFORE its LDS buffer is refilled, interleaved with the MFMAs. With the
 // whole step register-resident, two 64 KB LDS buffers carry a global prefetch
 // two K-steps deep (step kt+2 streams into the buffer step kt was read from),
 // so every LDS-DMA piece has ~1.5 K-steps (~3000 cycles) to land.
@@ -807,16 +363,30 @@ __global__ __launch_bounds__(NT5, 1) void pgemm5_kernel(const uint16_t* __restri
 // 16-B chunk c of row r sits at slot c ^ ((r >> 1) & 7) (source-side swizzle,
 // conflict-free for the 16 x 16 x 32 operand reads).
 constexpr int NT6 = 256;
-// RB6: half-1 MFMA index of the first read of the next step (its barrier one before);
-// AUX6: cache-policy bits of the LDS-DMA loads (0, or 16 = sc1 as hipBLASLt's kernels use)
 constexpr int OPB6 = BM * BK * 2;  // 32 KB per operand per K-step
 constexpr int BUF6 = 2 * OPB6;     // 64 KB
 
-template <int EPI, int RB6 = 37, int AUX6 = 0>
+// The 64 accumulators (256 registers) fill the accumulator file exactly; through the
+// builtin, hipcc's register allocator re-homes loop-carried accumulators every
+// iteration (~100-450 v_accvgpr moves per 64 MFMAs, with MFMA-result read stalls).
+// As an asm statement with the accumulator TIED in an AGPR ("+a") every tile stays
+// in place (0 moves). Hazards the compiler cannot see: an MFMA result read by a
+// non-MFMA instruction needs 12 wait states (8-pass XDL) -> mfma_drain() before the
+// epilogue; the A/B operands come straight from ds_read (lgkmcnt-ordered by hipcc,
+// which tracks the asm's "v" inputs), never from a VALU write in the 2 states before.
+__device__ __forceinline__ void mfma16_acc(f32x4_t& acc, const s16x8_t& a, const s16x8_t& b) {
+  asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b));
+}
+__device__ __forceinline__ void mfma_drain() { asm volatile("s_nop 7\n\ts_nop 7" ::: "memory"); }
+
+// Same launch forms as pgemm_kernel (tile0 / nsplit / ws).
+template <int EPI>
 __global__ __launch_bounds__(NT6, 1) void pgemm6_kernel(const uint16_t* __restrict__ A, int64_t lda,
                                                         const uint16_t* __restrict__ W, int64_t ldw,
                                                         uint16_t* __restrict__ C, int64_t ldc, int M, int N, int K,
                                                         int tile0, int nsplit, float* __restrict__ ws) {
+  // half-1 MFMA index of the first fragment read of the next step (its barrier one before)
+  constexpr int RB = 37;
   __shared__ __attribute__((aligned(1024))) char lds[2 * BUF6];  // the ONLY LDS object
   const int tiles_m = (M + BM - 1) / BM, tiles_n = N / BN;
   const int b = xcd_remap(blockIdx.x, gridDim.x);
@@ -853,7 +423,7 @@ __global__ __launch_bounds__(NT6, 1) void pgemm6_kernel(const uint16_t* __restri
     const uint32_t so = (uint32_t)(min(kt, nk - 1) * BK * 2);
     char* dst = lds + (kt & 1) * BUF6 + (wop ? OPB6 : 0) + (8 * w + j) * 1024;
     __builtin_amdgcn_raw_ptr_buffer_load_lds(wop ? rw : ra, (__attribute__((address_space(3))) void*)dst, 16,
-                                             wop ? vw[j] : va[j], so, 0, AUX6);
+                                             wop ? vw[j] : va[j], so, 0, 0);
   };
 
   // fragment reads: row 16 t + (lane & 15), chunk 4 h + (lane >> 4) at slot chunk ^ ((lane >> 1) & 7)
@@ -935,15 +505,15 @@ __global__ __launch_bounds__(NT6, 1) void pgemm6_kernel(const uint16_t* __restri
       mfma16_acc(acc[i][j], fw1[j], fa1[i]);
       if (t < 36 && t % 5 == 0) {
         dma(kt + 2, t / 5, true);
-      } else if (t == RB6 - 1) {
+      } else if (t == RB - 1) {
         asm volatile("s_waitcnt vmcnt(16)" ::: "memory");  // step kt+1 landed (this step's 16 in flight)
         bar();
-      } else if (t == RB6) {
+      } else if (t == RB) {
         fa0[0] = *reinterpret_cast<const s16x8_t*>(nxt + a_rd + rd0);
-      } else if (t > RB6 && t < RB6 + 9) {
-        fw0[t - RB6 - 1] = *reinterpret_cast<const s16x8_t*>(nxt + w_rd + (t - RB6 - 1) * 2048 + rd0);
-      } else if (t >= RB6 + 9 && t < RB6 + 16) {
-        fa0[t - RB6 - 8] = *reinterpret_cast<const s16x8_t*>(nxt + a_rd + (t - RB6 - 8) * 2048 + rd0);
+      } else if (t > RB && t < RB + 9) {
+        fw0[t - RB - 1] = *reinterpret_cast<const s16x8_t*>(nxt + w_rd + (t - RB - 1) * 2048 + rd0);
+      } else if (t >= RB + 9 && t < RB + 16) {
+        fa0[t - RB - 8] = *reinterpret_cast<const s16x8_t*>(nxt + a_rd + (t - RB - 8) * 2048 + rd0);
       }
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -963,6 +533,8 @@ __global__ __launch_bounds__(NT6, 1) void pgemm6_kernel(const uint16_t* __restri
     return;
   }
   __syncthreads();
+  // epilogue: acc[i][j][r] = C[m][n], m = wr*128 + 16 i + (lane & 15), n = wc*128 + 16 j + 4 (lane >> 4) + r.
+  // wave image: [128 rows][128 cols] bf16 (256-B rows), 16-B chunks XOR-swizzled by row & 15
   char* img = lds + w * 32768;
 #pragma unroll
   for (int i = 0; i < 8; ++i)
@@ -985,6 +557,8 @@ __global__ __launch_bounds__(NT6, 1) void pgemm6_kernel(const uint16_t* __restri
       if (m < M) *reinterpret_cast<u32x4_t*>(C + (int64_t)m * ldc + n0 + wc * 128 + c * 8) = v;
     }
   } else {
+    // EPI_SILU_STD: gate = tile columns [0, 128) (waves wc = 0), up = [128, 256) (wc = 1): both
+    // waves of a row half store 64 rows each of silu(g) * u
     const char* gimg = lds + (wr * 2) * 32768;
     const char* uimg = gimg + 32768;
 #pragma unroll 4
@@ -1234,7 +808,8 @@ __global__ __launch_bounds__(256) void pgemm_splitk_reduce(const float* __restri
 
 constexpr int PG_CUS = 256;  // MI355X compute units: one 256 x 256 tile per CU per wave
 
-// tail split plan of the 4-wave kernel: (tiles run data-parallel, tail tiles, splits) or splits 1
+// tail split plan (every variant): (tiles run data-parallel, tail tiles, splits) or splits 1;
+// only the plain epilogue splits
 __host__ inline void pgemm_plan(int M, int N, int K, int epi, int& full, int& tail, int& nsplit) {
   const int ntiles = ((M + BM - 1) / BM) * (N / BN), nk = K / BK;
   full = ntiles;
@@ -1251,135 +826,71 @@ __host__ inline void pgemm_plan(int M, int N, int K, int epi, int& full, int& ta
   nsplit = s;
 }
 
+// one tile (nsplit == 1) or one K-range of a tail tile per workgroup: (..., tile0, nsplit, ws)
+using TileKernel = void (*)(const uint16_t*, int64_t, const uint16_t*, int64_t, uint16_t*, int64_t, int, int, int, int,
+                            int, float*);
+// min(tiles, CUs) workgroups walking all `ntiles`: (..., ntiles)
+using PersistentKernel = void (*)(const uint16_t*, int64_t, const uint16_t*, int64_t, uint16_t*, int64_t, int, int,
+                                  int, int);
+
+// The kernels of one variant. Per epilogue the data-parallel kernel is tiled or persistent
+// (both null: the variant does not have that epilogue); the split-K tail is always tiled.
+struct PgemmKernels {
+  int threads;        // block size of every kernel of the set
+  bool byte_offsets;  // buffer-descriptor DMA: operand offsets are 31-bit BYTE offsets
+  TileKernel none, silu;
+  PersistentKernel persistent_none, persistent_silu;
+  TileKernel f32;
+};
+
+const PgemmKernels* pgemm_kernels(int variant) {
+  static const PgemmKernels v0 = {NT, false, pgemm_kernel<EPI_NONE>, nullptr, nullptr, nullptr, pgemm_kernel<EPI_F32>};
+  static const PgemmKernels v3 = {
+      NT6, true, pgemm6_kernel<EPI_NONE>, pgemm6_kernel<EPI_SILU_STD>, nullptr, nullptr, pgemm6_kernel<EPI_F32>};
+  static const PgemmKernels v6 = {
+      NT6, true, nullptr, nullptr, pgemm7_kernel<EPI_NONE>, pgemm7_kernel<EPI_SILU_STD>, pgemm6_kernel<EPI_F32>};
+  return variant == 0 ? &v0 : variant == 3 ? &v3 : variant == 6 ? &v6 : nullptr;
+}
+
 }  // namespace
 
-extern "C" int64_t llmd_pgemm_ws_bytes(int M, int N, int K, int epi, int variant) {
+extern "C" int64_t llmd_pgemm_ws_bytes(int M, int N, int K, int epi) {
   if (M <= 0 || N % BN || K % BK) return 0;
   int full, tail, nsplit;
   pgemm_plan(M, N, K, epi, full, tail, nsplit);
   return nsplit > 1 ? (int64_t)nsplit * tail * BM * BN * 4 : 0;
 }
 
-// variant 0: 8-wave staggered 4-phase kernel; 1: 4-wave 128 x 128-per-wave kernel (+ split-K tail when
-// ws is given: see pgemm_plan)
+// variant 0: 8-wave staggered 4-phase kernel; 3: PGR2; 6: persistent PGR2. epi: EPI_NONE, or
+// EPI_SILU_STD on variants 3 and 6; anything else returns -3 before any launch. With ws given
+// (llmd_pgemm_ws_bytes) a last wave of tiles at most half full runs split over K: see pgemm_plan.
 extern "C" int llmd_pgemm(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, int M, int N,
                           int K, int epi, int variant, void* ws, hipStream_t st) {
   if (M <= 0) return 0;
   if (N % BN || K % BK || lda % 8 || ldw % 8 || ldc % 8) return -1;
-  if (epi == EPI_SILU_STD && (variant < 3 || variant > 6)) return -3;
-  // 32-bit DMA offsets
-  if ((int64_t)(M - 1) * lda + K > 0x7fffffffLL || (int64_t)(N - 1) * ldw + K > 0x7fffffffLL) return -2;
-  const int ntiles = ((M + BM - 1) / BM) * (N / BN);
-  if (variant == 6) {
-    if (((int64_t)(M - 1) * lda + K) * 2 > 0x7fffffffLL || ((int64_t)(N - 1) * ldw + K) * 2 > 0x7fffffffLL) return -2;
-    int full = ntiles, tail = 0, nsplit = 1;
-    if (ws != nullptr) pgemm_plan(M, N, K, epi == EPI_SILU_STD ? EPI_SILU : epi, full, tail, nsplit);
-    const auto* a = (const uint16_t*)A;
-    const auto* w = (const uint16_t*)W;
-    auto* c = (uint16_t*)C;
-    const int P = std::min(full, PG_CUS);
-    if (epi == EPI_SILU_STD)
-      hipLaunchKernelGGL(pgemm7_kernel<EPI_SILU_STD>, dim3(P), dim3(NT6), 0, st, a, lda, w, ldw, c, ldc, M, N, K, full);
-    else if (epi == EPI_NONE && full > 0)
-      hipLaunchKernelGGL(pgemm7_kernel<EPI_NONE>, dim3(P), dim3(NT6), 0, st, a, lda, w, ldw, c, ldc, M, N, K, full);
-    else if (epi != EPI_NONE)
-      return -3;
-    if (nsplit > 1) {
-      hipLaunchKernelGGL((pgemm6_kernel<EPI_F32, 37, 0>), dim3(tail * nsplit), dim3(NT6), 0, st, a, lda, w, ldw, c, ldc,
-                         M, N, K, full, nsplit, (float*)ws);
-      hipLaunchKernelGGL(pgemm_splitk_reduce, dim3(tail * (BM / 8)), dim3(256), 0, st, (const float*)ws, nsplit,
-                         tail, full, c, ldc, M, N);
-    }
-    return (int)hipGetLastError();
-  }
-  if (variant >= 3 && variant <= 5) {
-    // buffer offsets are 31-bit byte offsets
-    if (((int64_t)(M - 1) * lda + K) * 2 > 0x7fffffffLL || ((int64_t)(N - 1) * ldw + K) * 2 > 0x7fffffffLL) return -2;
-    int full = ntiles, tail = 0, nsplit = 1;
-    if (ws != nullptr) pgemm_plan(M, N, K, epi, full, tail, nsplit);
-    const auto* a = (const uint16_t*)A;
-    const auto* w = (const uint16_t*)W;
-    auto* c = (uint16_t*)C;
-    // 3: reads of the next step from half-1 MFMA 37; 4: + sc1 LDS-DMA loads; 5: reads from MFMA 44
-    auto launch = [&](auto k_silu, auto k_std, auto k_none, auto k_f32) {
-      if (epi == EPI_SILU)
-        hipLaunchKernelGGL(k_silu, dim3(full), dim3(NT6), 0, st, a, lda, w, ldw, c, ldc, M, N, K, 0, 1, nullptr);
-      else if (epi == EPI_SILU_STD)
-        hipLaunchKernelGGL(k_std, dim3(full), dim3(NT6), 0, st, a, lda, w, ldw, c, ldc, M, N, K, 0, 1, nullptr);
-      else if (full > 0)
-        hipLaunchKernelGGL(k_none, dim3(full), dim3(NT6), 0, st, a, lda, w, ldw, c, ldc, M, N, K, 0, 1, nullptr);
-      if (nsplit > 1) {
-        hipLaunchKernelGGL(k_f32, dim3(tail * nsplit), dim3(NT6), 0, st, a, lda, w, ldw, c, ldc, M, N, K, full,
-                           nsplit, (float*)ws);
-        hipLaunchKernelGGL(pgemm_splitk_reduce, dim3(tail * (BM / 8)), dim3(256), 0, st, (const float*)ws, nsplit,
-                           tail, full, c, ldc, M, N);
-      }
-    };
-    if (variant == 3)
-      launch(pgemm6_kernel<EPI_SILU, 37, 0>, pgemm6_kernel<EPI_SILU_STD, 37, 0>, pgemm6_kernel<EPI_NONE, 37, 0>,
-             pgemm6_kernel<EPI_F32, 37, 0>);
-    else if (variant == 4)
-      launch(pgemm6_kernel<EPI_SILU, 37, 16>, pgemm6_kernel<EPI_SILU_STD, 37, 16>, pgemm6_kernel<EPI_NONE, 37, 16>,
-             pgemm6_kernel<EPI_F32, 37, 16>);
-    else
-      launch(pgemm6_kernel<EPI_SILU, 44, 0>, pgemm6_kernel<EPI_SILU_STD, 44, 0>, pgemm6_kernel<EPI_NONE, 44, 0>,
-             pgemm6_kernel<EPI_F32, 44, 0>);
-    return (int)hipGetLastError();
-  }
-  if (variant == 2) {
-    int full = ntiles, tail = 0, nsplit = 1;
-    if (ws != nullptr) pgemm_plan(M, N, K, epi, full, tail, nsplit);
-    const auto* a = (const uint16_t*)A;
-    const auto* w = (const uint16_t*)W;
-    auto* c = (uint16_t*)C;
-    if (epi == EPI_SILU)
-      hipLaunchKernelGGL(pgemm5_kernel<EPI_SILU>, dim3(full), dim3(NT5), 0, st, a, lda, w, ldw, c, ldc, M, N, K, 0, 1,
-                         nullptr);
-    else if (full > 0)
-      hipLaunchKernelGGL(pgemm5_kernel<EPI_NONE>, dim3(full), dim3(NT5), 0, st, a, lda, w, ldw, c, ldc, M, N, K, 0, 1,
-                         nullptr);
-    if (nsplit > 1) {
-      hipLaunchKernelGGL(pgemm5_kernel<EPI_F32>, dim3(tail * nsplit), dim3(NT5), 0, st, a, lda, w, ldw, c, ldc, M, N,
-                         K, full, nsplit, (float*)ws);
-      hipLaunchKernelGGL(pgemm_splitk_reduce, dim3(tail * (BM / 8)), dim3(256), 0, st, (const float*)ws, nsplit,
-                         tail, full, c, ldc, M, N);
-    }
-    return (int)hipGetLastError();
-  }
-  if (variant == 1) {
-    int full = ntiles, tail = 0, nsplit = 1;
-    if (ws != nullptr) pgemm_plan(M, N, K, epi, full, tail, nsplit);
-    const auto* a = (const uint16_t*)A;
-    const auto* w = (const uint16_t*)W;
-    auto* c = (uint16_t*)C;
-    if (epi == EPI_SILU)
-      hipLaunchKernelGGL(pgemm4_kernel<EPI_SILU>, dim3(full), dim3(NT4), 0, st, a, lda, w, ldw, c, ldc, M, N, K, 0, 1,
-                         nullptr);
-    else if (full > 0)
-      hipLaunchKernelGGL(pgemm4_kernel<EPI_NONE>, dim3(full), dim3(NT4), 0, st, a, lda, w, ldw, c, ldc, M, N, K, 0, 1,
-                         nullptr);
-    if (nsplit > 1) {
-      hipLaunchKernelGGL(pgemm4_kernel<EPI_F32>, dim3(tail * nsplit), dim3(NT4), 0, st, a, lda, w, ldw, c, ldc, M, N,
-                         K, full, nsplit, (float*)ws);
-      hipLaunchKernelGGL(pgemm_splitk_reduce, dim3(tail * (BM / 8)), dim3(256), 0, st, (const float*)ws, nsplit,
-                         tail, full, c, ldc, M, N);
-    }
-    return (int)hipGetLastError();
-  }
-  int full = ntiles, tail = 0, nsplit = 1;
-  if (ws != nullptr) pgemm_plan(M, N, K, epi, full, tail, nsplit);
+  const PgemmKernels* ks = pgemm_kernels(variant);
+  if (ks == nullptr || (epi != EPI_NONE && epi != EPI_SILU_STD)) return -3;
+  const TileKernel tiled = epi == EPI_NONE ? ks->none : ks->silu;
+  const PersistentKernel persistent = epi == EPI_NONE ? ks->persistent_none : ks->persistent_silu;
+  if (tiled == nullptr && persistent == nullptr) return -3;
+  // 32-bit element offsets of the DMA sources; 31-bit byte offsets of the buffer descriptors
+  const int64_t amax = (int64_t)(M - 1) * lda + K, wmax = (int64_t)(N - 1) * ldw + K;
+  if (amax > 0x7fffffffLL || wmax > 0x7fffffffLL) return -2;
+  if (ks->byte_offsets && (amax * 2 > 0x7fffffffLL || wmax * 2 > 0x7fffffffLL)) return -2;
+
+  int full = ((M + BM - 1) / BM) * (N / BN), tail = 0, nsplit = 1;
+  if (ws != nullptr) pgemm_plan(M, N, K, epi, full, tail, nsplit);  // EPI_SILU_STD: no split
   const auto* a = (const uint16_t*)A;
   const auto* w = (const uint16_t*)W;
   auto* c = (uint16_t*)C;
-  if (epi == EPI_SILU)
-    hipLaunchKernelGGL(pgemm_kernel<EPI_SILU>, dim3(full), dim3(NT), 0, st, a, lda, w, ldw, c, ldc, M, N, K, 0, 1,
-                       nullptr);
+  if (full > 0 && tiled != nullptr)
+    hipLaunchKernelGGL(tiled, dim3(full), dim3(ks->threads), 0, st, a, lda, w, ldw, c, ldc, M, N, K, 0, 1, nullptr);
   else if (full > 0)
-    hipLaunchKernelGGL(pgemm_kernel<EPI_NONE>, dim3(full), dim3(NT), 0, st, a, lda, w, ldw, c, ldc, M, N, K, 0, 1,
-                       nullptr);
+    hipLaunchKernelGGL(persistent, dim3(std::min(full, PG_CUS)), dim3(ks->threads), 0, st, a, lda, w, ldw, c, ldc, M,
+                       N, K, full);
   if (nsplit > 1) {
-    hipLaunchKernelGGL(pgemm_kernel<EPI_F32>, dim3(tail * nsplit), dim3(NT), 0, st, a, lda, w, ldw, c, ldc, M, N, K,
-                       full, nsplit, (float*)ws);
+    hipLaunchKernelGGL(ks->f32, dim3(tail * nsplit), dim3(ks->threads), 0, st, a, lda, w, ldw, c, ldc, M, N, K, full,
+                       nsplit, (float*)ws);
     hipLaunchKernelGGL(pgemm_splitk_reduce, dim3(tail * (BM / 8)), dim3(256), 0, st, (const float*)ws, nsplit, tail,
                        full, c, ldc, M, N);
   }

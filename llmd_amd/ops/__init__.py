@@ -1374,21 +1374,23 @@ def mgemm_ok(x: torch.Tensor, w: torch.Tensor, max_m: int = 256) -> bool:
 _MGEMM_MS = (64, 96, 128, 192, 256)
 
 
-PGEMM_VARIANT = int(os.environ.get("LLMD_PGEMM_VARIANT", "0"))
+PGEMM_VARIANTS = (0, 3, 6)     # 8-wave kernel, PGR2, persistent PGR2 (csrc/ops/pgemm.hip)
+PGEMM_SILU_VARIANTS = (3, 6)   # those with the fused SiLU-and-mul epilogue (epi 3)
 
 
 def pgemm(x: torch.Tensor, w: torch.Tensor, epi: int = 0, out: Optional[torch.Tensor] = None,
           variant: Optional[int] = None, split_k: bool = True) -> torch.Tensor:
     """Y = X W^T on the prefill GEMM (csrc/ops/pgemm.hip: 256 x 256 LDS-DMA MFMA
-    tiles; N % 256 == 0, K % 64 == 0, any M). epi=1: ``w`` holds gate/up rows
-    interleaved per 256-row tile (pgemm_pack_gate_up) and the kernel stores
-    silu(gate) * up, [M, N / 2]. ``split_k`` (variant 1, epi 0): a last wave of
-    tiles at most half full runs split over K (fp32 partials + reduce)."""
+    tiles; N % 256 == 0, K % 64 == 0, any M). ``variant``: one of PGEMM_VARIANTS
+    (None: 0). epi=3 (PGEMM_SILU_VARIANTS only, see pgemm_silu): ``w`` is a
+    [gate; up] weight and the kernel stores silu(gate) * up, [M, N / 2].
+    ``split_k`` (epi 0): a last wave of tiles at most half full runs split over
+    K (fp32 partials + reduce). Any other variant or epi raises RuntimeError."""
     M = x.shape[0]
     N = w.shape[0]
     if out is None:
-        out = torch.empty(M, N // 2 if epi in (1, 3) else N, dtype=x.dtype, device=x.device)
-    native().pgemm(out, x, w, epi, PGEMM_VARIANT if variant is None else variant, split_k)
+        out = torch.empty(M, N // 2 if epi == 3 else N, dtype=x.dtype, device=x.device)
+    native().pgemm(out, x, w, epi, 0 if variant is None else variant, split_k)
     return out
 
 
@@ -1397,17 +1399,6 @@ def pgemm_silu(x: torch.Tensor, w: torch.Tensor, variant: int = 3, out: Optional
     weight ([2F, K], F % 128 == 0): each 256-column tile loads 128 gate rows and the matching
     128 up rows, the epilogue stores the activation [M, F] (no [M, 2F] round trip, no act kernel)."""
     return pgemm(x, w, epi=3, out=out, variant=variant, split_k=False)
-
-
-def pgemm_pack_gate_up(w: torch.Tensor) -> torch.Tensor:
-    """[2F, K] (gate rows, then up rows) -> the fused-SiLU pgemm layout: per
-    256-row tile, 128 gate rows then the matching 128 up rows (F % 128 == 0)."""
-    F2, K = w.shape
-    F = F2 // 2
-    assert F % 128 == 0, F
-    g = w[:F].view(F // 128, 128, K)
-    u = w[F:].view(F // 128, 128, K)
-    return torch.stack((g, u), 1).reshape(F2, K).contiguous()
 
 
 def pgemm_ok(x: torch.Tensor, w: torch.Tensor) -> bool:
@@ -1433,21 +1424,9 @@ def mgemm_choice(M: int, N: int, K: int) -> Optional[tuple[int, int, int]]:
 # SHAPE. The choice is a STATIC table measured offline (ops/pgemm_table.py, written by
 # scripts/make_pgemm_table.py): keyed by (M bucket of 256 rows, N, K), so every run and every
 # TP / EP rank picks the same kernel and no forward ever stalls on a timing run.
-# LLMD_PGEMM_AUTO=measure restores the old first-sight timing (tuning only); =0 disables pgemm.
+# LLMD_PGEMM_AUTO=0 disables pgemm; LLMD_PGEMM_MIN_M is the smallest M that looks at the table.
 PGEMM_AUTO = os.environ.get("LLMD_PGEMM_AUTO", "table")
 PGEMM_MIN_M = int(os.environ.get("LLMD_PGEMM_MIN_M", "256"))
-_pgemm_pick: dict = {}
-
-
-def _time_ms(fn, reps: int = 2) -> float:
-    fn()
-    st, en = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    st.record()
-    for _ in range(reps):
-        fn()
-    en.record()
-    en.synchronize()
-    return st.elapsed_time(en) / reps
 
 
 def pgemm_plan(M: int, N: int, K: int) -> Optional[tuple[int, bool]]:
@@ -1470,30 +1449,6 @@ def pgemm_silu_plan(x: torch.Tensor, w: torch.Tensor) -> Optional[int]:
     return None if e is None or e[0] is None else e[0][0]
 
 
-def pgemm_wins(x: torch.Tensor, w: torch.Tensor) -> Optional[tuple[int, bool]]:
-    """The pgemm plan for this GEMM, or None for hipBLASLt."""
-    M, (N, K) = x.shape[0], w.shape
-    if PGEMM_AUTO != "measure":
-        return pgemm_plan(M, N, K)
-    key = ((M + 255) // 256, N, K)
-    c = _pgemm_pick.get(key, False)
-    if c is False:
-        if torch.cuda.is_current_stream_capturing():
-            return None
-        y = torch.empty(M, N, dtype=x.dtype, device=x.device)
-        t_pg = _time_ms(lambda: pgemm(x, w, out=y))
-        t_bl = _time_ms(lambda: torch.nn.functional.linear(x, w))
-        c = _pgemm_pick[key] = (PGEMM_VARIANT, True) if t_pg < 0.97 * t_bl else None
-        msg = (f"prefill GEMM M~{M} N={N} K={K}: pgemm {t_pg:.3f} ms, hipBLASLt {t_bl:.3f} ms -> "
-               f"{'pgemm' if c else 'hipBLASLt'}")
-        log.debug(msg)
-        if os.environ.get("LLMD_PGEMM_VERBOSE") == "1":
-            import sys
-
-            print(msg, file=sys.stderr, flush=True)
-    return c
-
-
 def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Dense projection: decode-sized M on our decode GEMM kernels where their
     measured dispatch tables have them ahead of hipBLASLt - the medium-M LDS-DMA
@@ -1502,7 +1457,7 @@ def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None
     prefill-sized M on the prefill GEMM where the shipped table (ops/pgemm_table.py)
     has it ahead of hipBLASLt - everything else on hipBLASLt."""
     if PGEMM_AUTO != "0" and x.dim() == 2 and x.shape[0] >= PGEMM_MIN_M and pgemm_ok(x, w):
-        plan = pgemm_wins(x, w)
+        plan = pgemm_plan(x.shape[0], w.shape[0], w.shape[1])
         if plan is not None:
             y = pgemm(x, w, variant=plan[0], split_k=plan[1])
             return y if bias is None else y.add_(bias)

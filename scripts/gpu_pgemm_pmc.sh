@@ -14,7 +14,7 @@ import csv, glob, collections
 def kind(n):
     if "Cijk" in n:
         return "blas"
-    for v in ("pgemm6", "pgemm5", "pgemm4"):
+    for v in ("pgemm7", "pgemm6"):
         if v in n:
             return v
     return "pgemm0" if "pgemm_kernel" in n else None

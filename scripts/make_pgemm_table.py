@@ -7,7 +7,7 @@ rounds in one process, and keep a pgemm plan only where it beats hipBLASLt by
 >= --margin. The engine then picks by table lookup - the same choice on every
 run and every TP / EP rank, no timing inside a forward.
 
-  python scripts/make_pgemm_table.py [--rounds 3] [--variants 0,3] [--out llmd_amd/ops/pgemm_table.py]
+  python scripts/make_pgemm_table.py [--rounds 3] [--variants 0,3,6] [--out llmd_amd/ops/pgemm_table.py]
 """
 from __future__ import annotations
 
@@ -48,7 +48,7 @@ def timeit(fn, iters):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--variants", default="0,3")
+    ap.add_argument("--variants", default="0,3,6")
     ap.add_argument("--models", default=",".join(SHAPES))
     ap.add_argument("--buckets", default=",".join(map(str, BUCKETS)))
     ap.add_argument("--margin", type=float, default=0.03)
@@ -86,7 +86,7 @@ def main():
                 ya = torch.empty(M, N // 2, device="cuda", dtype=torch.bfloat16)
                 fc = {"blas+act": lambda: ops.gated_act(F.linear(x, w), ops.ACT_SILU)}
                 for v in vs:
-                    if v >= 3:
+                    if v in ops.PGEMM_SILU_VARIANTS:
                         fc[(v, False)] = (lambda v=v: ops.pgemm_silu(x, w, variant=v, out=ya))
                 fr = {k: [] for k in fc}
                 for _ in range(a.rounds):

@@ -16,7 +16,7 @@ ap.add_argument("--m", type=int, default=4608)
 ap.add_argument("--n", type=int, default=10240)
 ap.add_argument("--k", type=int, default=8192)
 ap.add_argument("--iters", type=int, default=20)
-ap.add_argument("--variants", default="0,2")
+ap.add_argument("--variants", default="0,3")
 a = ap.parse_args()
 x = torch.rand(a.m, a.k, device="cuda").mul_(2).sub_(1).to(torch.bfloat16)
 w = torch.rand(a.n, a.k, device="cuda").mul_(2).sub_(1).to(torch.bfloat16)

@@ -51,6 +51,22 @@ def test_mgemm_table_entries_and_buckets():
     assert ops.mgemm_choice(64, 1234, 4096) is None
 
 
+def test_pgemm_table_names_only_built_variants():
+    """Every plan of the prefill GEMM table is None or (variant, split_k) with a variant the
+    library has; the fused-SiLU entries name a variant with that epilogue and never split."""
+    from llmd_amd.ops.pgemm_table import PGEMM_TABLE
+
+    assert PGEMM_TABLE
+    for key, entry in PGEMM_TABLE.items():
+        plan = entry[0]
+        if plan is None:
+            continue
+        v, split_k = plan
+        assert v in ops.PGEMM_VARIANTS and isinstance(split_k, bool), (key, plan)
+        if key[0] == "silu":
+            assert v in ops.PGEMM_SILU_VARIANTS and split_k is False, (key, plan)
+
+
 def test_moe_tile_version_choice(monkeypatch):
     """Persistent expert-tile GEMM (moe8) choice: fp8 from 4 K-steps of 128, bf16 only for 4 .. 4096-deep
     K (gpt-oss 2880 yes, DeepSeek gate/up 7168 no), both switchable off."""
