@@ -91,11 +91,15 @@ struct TileState {
   float m[NP], lsum[NP];
 };
 
-template <int D, bool F8, int NP, bool NTL = false>
+// PC (verify rows): this lane's column of pass p sees only keys [clo[p], chi[p])
+// of the tile range [s0, s1). A column may then have a whole tile, or the whole
+// range, masked: its running max stays -inf and the rescale is guarded.
+template <int D, bool F8, int NP, bool NTL = false, bool PC = false>
 __device__ __forceinline__ void attend_tiles(TileState<D, F8, NP>& st, const void* __restrict__ kc,
                                              const void* __restrict__ vc, int64_t block_stride, int bs,
                                              const int* __restrict__ bt, int64_t head_off, int s0, int s1,
-                                             float scale_log2, char* vimg, int w, int lane) {
+                                             float scale_log2, char* vimg, int w, int lane,
+                                             const int* clo = nullptr, const int* chi = nullptr) {
   using CR = typename CacheReg<F8>::T;
   constexpr int KS = D / 32;   // k-steps of the QK^T product
   constexpr int NB = D / 16;   // 16-wide dim blocks of the PV product
@@ -162,20 +166,29 @@ __device__ __forceinline__ void attend_tiles(TileState<D, F8, NP>& st, const voi
         for (int i = 0; i < 4; ++i) {
           const int key = ts + 16 * b4 + rowoff(g) + i;
           float v = sc[p][b4][i] * scale_log2;
-          v = key < s1 ? v : NEG_INF;
+          if constexpr (PC)
+            v = (key >= clo[p] && key < chi[p]) ? v : NEG_INF;  // chi <= L, and s1 <= L
+          else
+            v = key < s1 ? v : NEG_INF;
           sc[p][b4][i] = v;
           mx = fmaxf(mx, v);
         }
       mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
       mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
       const float mnew = fmaxf(st.m[p], mx);
-      const float alpha = exp2f(st.m[p] - mnew);
+      float alpha, msub = mnew;
+      if constexpr (PC) {  // no key seen yet: -inf - -inf would be NaN
+        alpha = (mnew == NEG_INF) ? 1.f : exp2f(st.m[p] - mnew);
+        msub = (mnew == NEG_INF) ? 0.f : mnew;
+      } else {
+        alpha = exp2f(st.m[p] - mnew);
+      }
       float ps = 0.f;
 #pragma unroll
       for (int b4 = 0; b4 < 4; ++b4)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-          const float pv = exp2f(sc[p][b4][i] - mnew);
+          const float pv = exp2f(sc[p][b4][i] - msub);
           sc[p][b4][i] = pv;
           ps += pv;
         }
@@ -346,6 +359,98 @@ __global__ __launch_bounds__(NT, 2) void paged_decode_kernel(
       }
     }
   });
+}
+
+// Speculative-decoding verify: the Q = q_len[b] <= 8 newest tokens of sequence
+// b (rows q_start[b] .. of `q`; seq_lens[b] is the context of the last one)
+// attend in one pass over the sequence's K/V. Column c of the sequence's Q*G
+// columns is token c / G, head c % G of this KV head; a workgroup takes 16*NP
+// of them (column group blockIdx.y / Hkv: with 8 KV heads and one split the
+// groups of one (sequence, KV head) get workgroup ids 8 apart, which the
+// dispatcher places on the same XCD, so the groups after the first find the
+// K/V in that XCD's L2) and token j sees keys
+// [start_j, L - (Q-1) + j), start_j its sliding-window start. The tile loop
+// runs over the union [start_0, L) cut into splits; partials use the decode
+// workspace layout with one row per query token.
+template <int D, bool F8, int NP, bool NTL = false>
+__global__ __launch_bounds__(NT, NP == 1 ? 2 : 1) void paged_verify_kernel(
+    const uint16_t* __restrict__ q, int64_t q_stride, const void* __restrict__ kc,
+    const void* __restrict__ vc, int64_t block_stride, int bs,
+    const int* __restrict__ block_tables, int bt_stride, const int* __restrict__ seq_lens,
+    const int* __restrict__ q_start, const int* __restrict__ q_len, int Hq, int Hkv, int G,
+    float scale_log2, int window, const float* __restrict__ sinks, int split_size, int nslot, int direct,
+    uint16_t* __restrict__ out, int64_t out_stride, float* __restrict__ part_o, float* __restrict__ part_ml,
+    float vscale) {
+  constexpr int KS = D / 32;
+  constexpr int NB = D / 16;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+
+  const int sp = blockIdx.x;
+  const int kvh = blockIdx.y % Hkv, cg = blockIdx.y / Hkv;
+  const int b = blockIdx.z;
+  const int L = seq_lens[b], Q = q_len[b], row0 = q_start[b];
+  LLMD_DCHECK(Q >= 1 && Q <= 8 && L >= Q && L <= bt_stride * bs && row0 >= 0);
+  const int ncol = Q * G, col0 = cg * 16 * NP;
+  if (col0 >= ncol) return;  // the grid is sized for the longest q_len of the batch
+  const int L0 = L - (Q - 1);  // context of the first token
+  const int start = window > 0 ? max(0, L0 - window) : 0;
+  const int s0 = start + sp * split_size;
+  if (s0 >= L) return;
+  const int s1 = min(s0 + split_size, L);
+
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int g = lane >> 4, c16 = lane & 15;
+  const int* bt = block_tables + (int64_t)b * bt_stride;
+  const int64_t head_off = (int64_t)kvh * bs * D;
+
+  TileState<D, F8, NP> st;
+  int clo[NP], chi[NP];
+#pragma unroll
+  for (int p = 0; p < NP; ++p) {
+    const int c = col0 + 16 * p + c16;
+    const bool valid = c < ncol;
+    const int j = valid ? c / G : 0;
+    chi[p] = valid ? L0 + j : 0;  // a padding column sees no key
+    clo[p] = window > 0 ? max(0, chi[p] - window) : 0;
+    const uint16_t* qr = q + (int64_t)(row0 + j) * q_stride + (int64_t)(kvh * G + (c - j * G)) * D;
+#pragma unroll
+    for (int s = 0; s < KS; ++s) {
+      u32x4_t v = {0, 0, 0, 0};
+      if (valid) v = *reinterpret_cast<const u32x4_t*>(qr + (4 * s + g) * 8);
+      st.qf[p][s] = __builtin_bit_cast(bf16x8_t, v);
+    }
+    st.m[p] = NEG_INF;
+    st.lsum[p] = 0.f;
+#pragma unroll
+    for (int n = 0; n < NB; ++n) st.o[p][n] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  }
+
+  attend_tiles<D, F8, NP, NTL, true>(st, kc, vc, block_stride, bs, bt, head_off, s0, s1, scale_log2,
+                                     smem + w * (64 * D * 2), w, lane, clo, chi);
+
+  // a column with every key of this split masked emits M = -inf, Ls = 0, O = 0
+#pragma unroll
+  for (int p = 0; p < NP; ++p)
+    merge_waves<D, F8, NP>(st, p, smem, w, lane, [&](int h, int d, float acc, float M, float Ls) {
+      const int c = col0 + 16 * p + h;
+      if (c >= ncol) return;
+      const int j = c / G;
+      const int hq = kvh * G + (c - j * G);
+      const int64_t row = row0 + j;
+      acc *= vscale;
+      if (direct) {  // one split: every token sees at least its own key, so M is finite
+        float den = Ls;
+        if (sinks) den += exp2f(sinks[hq] * 1.4426950408889634f - M);
+        out[row * out_stride + (int64_t)hq * D + d] = f2bf(acc / den);
+      } else {
+        const int64_t pi = (row * Hq + hq) * nslot + sp;
+        part_o[pi * D + d] = acc;
+        if (d == 0) {
+          part_ml[pi * 2] = M;
+          part_ml[pi * 2 + 1] = Ls;
+        }
+      }
+    });
 }
 
 // Shared-prefix ("cascade") decode: one work unit = up to 16*NP/G sequences
@@ -669,15 +774,28 @@ __global__ __launch_bounds__(NT, 2) void shared_prefix_v2_kernel(
 
 // Merge a sequence's partials: suffix splits [0, nact) and, with a shared
 // prefix, the prefix kernel's slots [pslot0, pslot0 + pcount[b]).
-template <int D>
+// VERIFY: token blockIdx.z of sequence b, workspace / output row q_start[b] + z;
+// its splits are those of paged_verify_kernel, over [start of the first token, L).
+// A split in which the token saw no key has M = -inf and O = 0 and so weight
+// exp2(-inf - M) = 0: M is finite, every token sees at least its own key.
+template <int D, bool VERIFY = false>
 __global__ __launch_bounds__(64) void decode_reduce_kernel(
     const float* __restrict__ part_o, const float* __restrict__ part_ml,
     const int* __restrict__ seq_lens, const int* __restrict__ sstart, const int* __restrict__ pcount,
     int Hq, int nsplit, int nslot, int split_size, const int* __restrict__ split_dev, int window,
-    const float* __restrict__ sinks, uint16_t* __restrict__ out, int64_t out_stride) {
-  const int hq = blockIdx.x, b = blockIdx.y;
+    const float* __restrict__ sinks, uint16_t* __restrict__ out, int64_t out_stride,
+    const int* __restrict__ q_start, const int* __restrict__ q_len) {
+  const int hq = blockIdx.x;
+  int b = blockIdx.y;
   const int L = seq_lens[b];
-  int start = window > 0 ? max(0, L - window) : 0;
+  int L0 = L;
+  if constexpr (VERIFY) {
+    const int Q = q_len[b];
+    if ((int)blockIdx.z >= Q) return;
+    L0 = L - (Q - 1);
+    b = q_start[b] + blockIdx.z;
+  }
+  int start = window > 0 ? max(0, L0 - window) : 0;
   if (sstart) start = max(start, sstart[b]);
   if (split_dev) split_size = *split_dev;
   const int nact = min(nsplit, (L - start + split_size - 1) / split_size);
@@ -754,7 +872,7 @@ extern "C" int llmd_paged_decode(const void* q, int64_t q_stride, const void* kc
       hipLaunchKernelGGL(decode_reduce_kernel<DD>, dim3(Hq, B), dim3(64), 0, st, part_o, part_ml, seq_lens,  \
                          cascade ? sstart : nullptr, cascade ? pcount : nullptr, Hq, nsplit,                 \
                          direct ? nsplit : nslot, split_size, split_dev, window, sinks, (uint16_t*)out,       \
-                         out_stride);                                                                        \
+                         out_stride, nullptr, nullptr);                                                      \
   } while (0)
   if (D == 128) {
     if (fp8) LAUNCH(128, true); else LAUNCH(128, false);
@@ -764,5 +882,60 @@ extern "C" int llmd_paged_decode(const void* q, int64_t q_stride, const void* kc
     return -1;
   }
 #undef LAUNCH
+  return 0;
+}
+
+// Verify rows of speculative decoding: sequence b owns rows q_start[b] .. + q_len[b] (<= max_q <= 8)
+// of q / out; the workspace holds nsplit slots per (row, head) when nsplit > 1. np: 16-column
+// passes per workgroup (1 or 2, chosen by ops.verify_passes).
+extern "C" int llmd_paged_verify(const void* q, int64_t q_stride, const void* kc, const void* vc,
+                                 int64_t block_stride, int bs, const int* block_tables, int bt_stride,
+                                 const int* seq_lens, const int* q_start, const int* q_len, int B, int max_q,
+                                 int np, int Hq, int Hkv, int D, float scale, int window, const float* sinks,
+                                 int split_size, int nsplit, void* out, int64_t out_stride, float* part_o,
+                                 float* part_ml, int fp8, float k_scale, float v_scale, hipStream_t st) {
+  if (B == 0) return 0;
+  const int G = Hq / Hkv;
+  if (G > 16 || max_q < 1 || max_q > 8 || np < 1 || np > 2) return -2;
+  const float scale_log2 = scale * k_scale * 1.4426950408889634f;
+  const int direct = nsplit == 1 ? 1 : 0;
+  // two 16-column passes per workgroup hold their accumulators without scratch, but at D = 128
+  // with one wave per SIMD; further column groups go on grid.y and re-read the K/V from L2
+  const int cols = max_q * G;
+  const int NCG = (cols + 16 * np - 1) / (16 * np);
+  dim3 grid(nsplit, Hkv * NCG, B), blk(NT);
+  const size_t lds = (size_t)4 * 64 * D * 2;
+  static const bool nt_env = [] {
+    const char* e = getenv("LLMD_DECODE_NT");
+    return !(e && e[0] == '0');
+  }();
+  // several column groups read the same K/V: the first group's lines should stay in L2 for the others
+  const bool nt = nt_env && NCG == 1;
+#define VLAUNCH1(DD, F8, NPP, NTLL)                                                                          \
+  hipLaunchKernelGGL((paged_verify_kernel<DD, F8, NPP, NTLL>), grid, blk, lds, st, (const uint16_t*)q,       \
+                     q_stride, kc, vc, block_stride, bs, block_tables, bt_stride, seq_lens, q_start, q_len,  \
+                     Hq, Hkv, G, scale_log2, window, sinks, split_size, nsplit, direct, (uint16_t*)out,      \
+                     out_stride, part_o, part_ml, v_scale)
+#define VLAUNCH(DD, F8)                                                                                      \
+  do {                                                                                                       \
+    if (np == 1) {                                                                                           \
+      if (nt) VLAUNCH1(DD, F8, 1, true); else VLAUNCH1(DD, F8, 1, false);                                    \
+    } else {                                                                                                 \
+      if (nt) VLAUNCH1(DD, F8, 2, true); else VLAUNCH1(DD, F8, 2, false);                                    \
+    }                                                                                                        \
+    if (!direct)                                                                                             \
+      hipLaunchKernelGGL((decode_reduce_kernel<DD, true>), dim3(Hq, B, max_q), dim3(64), 0, st, part_o,      \
+                         part_ml, seq_lens, nullptr, nullptr, Hq, nsplit, nsplit, split_size, nullptr,       \
+                         window, sinks, (uint16_t*)out, out_stride, q_start, q_len);                         \
+  } while (0)
+  if (D == 128) {
+    if (fp8) VLAUNCH(128, true); else VLAUNCH(128, false);
+  } else if (D == 64) {
+    if (fp8) VLAUNCH(64, true); else VLAUNCH(64, false);
+  } else {
+    return -1;
+  }
+#undef VLAUNCH
+#undef VLAUNCH1
   return 0;
 }

@@ -28,6 +28,9 @@ int llmd_paged_decode(const void*, int64_t, const void*, const void*, int64_t, i
                       const int*, int, int, int, int, float, int, const float*, int, int, void*,
                       int64_t, float*, float*, int, float, float, const int*, const int*, const int*,
                       const int*, int, int, int, const int*, hipStream_t);
+int llmd_paged_verify(const void*, int64_t, const void*, const void*, int64_t, int, const int*, int,
+                      const int*, const int*, const int*, int, int, int, int, int, int, float, int, const float*,
+                      int, int, void*, int64_t, float*, float*, int, float, float, hipStream_t);
 int llmd_paged_prefill(const void*, int64_t, const void*, const void*, int64_t, int, const int*, int,
                        const int*, const int*, const int*, const int*, int, int, int, int, float,
                        int, const float*, void*, int64_t, int, float, float, hipStream_t);
@@ -383,6 +386,52 @@ void paged_decode(torch::Tensor out, torch::Tensor q, torch::Tensor k_cache, tor
                              is_fp8_cache(k_cache) ? 1 : 0, (float)k_scale, (float)v_scale, sstart, pcount,
                              members, work, nwork, (int)np, (int)nslot, sdev, cur_stream());
   TORCH_CHECK(rc == 0, "paged_decode: unsupported head dim / cascade config, rc=", rc);
+}
+
+// speculative-decoding verify rows: q [T, >=Hq*D], out [T, Hq*D]; sequence b owns rows
+// q_start[b] .. q_start[b] + q_len[b] (1 <= q_len <= max_q <= 8), seq_lens[b] = context of its last row
+void paged_verify(torch::Tensor out, torch::Tensor q, torch::Tensor k_cache, torch::Tensor v_cache,
+                  torch::Tensor block_tables, torch::Tensor seq_lens, torch::Tensor q_start,
+                  torch::Tensor q_len, int64_t max_q, int64_t np, int64_t Hq, int64_t Hkv, int64_t D, double scale,
+                  int64_t window, c10::optional<torch::Tensor> sinks, int64_t split_size, int64_t nsplit,
+                  torch::Tensor part_o, torch::Tensor part_ml, double k_scale, double v_scale) {
+  const c10::hip::OptionalHIPGuard device_guard(dev_of(out));
+  CHECK_CUDA(q); CHECK_BF16(q); CHECK_BF16(out); CHECK_INNER(q); CHECK_INNER(out);
+  check_cache(k_cache, v_cache, Hkv, D);
+  CHECK_DT(block_tables, at::kInt); CHECK_DT(seq_lens, at::kInt);
+  CHECK_CUDA(q_start); CHECK_CUDA(q_len); CHECK_DT(q_start, at::kInt); CHECK_DT(q_len, at::kInt);
+  TORCH_CHECK(block_tables.dim() == 2 && block_tables.stride(1) == 1, "block_tables 2-D");
+  const int B = seq_lens.numel();
+  const int64_t T = q.size(0);
+  TORCH_CHECK(q_start.numel() == B && q_len.numel() == B && block_tables.size(0) >= B &&
+                  q_start.is_contiguous() && q_len.is_contiguous() && seq_lens.is_contiguous(),
+              "verify: batch mismatch");
+  TORCH_CHECK(Hq % Hkv == 0 && Hq / Hkv <= 16 && (D == 64 || D == 128), "verify: heads/D (G <= 16)");
+  TORCH_CHECK(max_q >= 1 && max_q <= 8 && (np == 1 || np == 2), "verify: q_len 1..8, 1 or 2 passes");
+  TORCH_CHECK(q.size(1) >= Hq * D && out.size(0) >= T && out.size(1) >= Hq * D, "verify: widths");
+  TORCH_CHECK(split_size % 64 == 0 && split_size > 0 && nsplit >= 1, "verify: split");
+  TORCH_CHECK(q.stride(0) % 8 == 0, "verify: 16-B aligned q rows");
+  const float* sk = nullptr;
+  if (sinks.has_value()) {
+    CHECK_DT(sinks.value(), at::kFloat);
+    TORCH_CHECK(sinks->numel() == Hq, "sinks [Hq]");
+    sk = sinks->data_ptr<float>();
+  }
+  if (nsplit > 1) {
+    CHECK_DT(part_o, at::kFloat); CHECK_DT(part_ml, at::kFloat);
+    TORCH_CHECK(part_o.numel() >= T * Hq * nsplit * D && part_ml.numel() >= T * Hq * nsplit * 2,
+                "verify workspace too small");
+  }
+  // the host guarantees q_start[b] + q_len[b] <= T, q_len[b] <= max_q and ctx <= nsplit*split_size
+  int rc = llmd_paged_verify(q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(),
+                             k_cache.stride(0), k_cache.size(2), block_tables.data_ptr<int>(),
+                             block_tables.stride(0), seq_lens.data_ptr<int>(), q_start.data_ptr<int>(),
+                             q_len.data_ptr<int>(), B, (int)max_q, (int)np, Hq, Hkv, D, (float)scale, (int)window, sk,
+                             split_size, nsplit, out.data_ptr(), out.stride(0),
+                             nsplit > 1 ? part_o.data_ptr<float>() : nullptr,
+                             nsplit > 1 ? part_ml.data_ptr<float>() : nullptr, is_fp8_cache(k_cache) ? 1 : 0,
+                             (float)k_scale, (float)v_scale, cur_stream());
+  TORCH_CHECK(rc == 0, "paged_verify: unsupported head dim / group size, rc=", rc);
 }
 
 // MLA (absorbed form): q [R, H*576], cache [blocks, bs, 576] (block stride free),
@@ -1353,6 +1402,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {  // _C, or _C_debug (llmd_amd/build.p
   m.def("rope_cache", &rope_cache);
   m.def("gated_act", &gated_act);
   m.def("paged_decode", &paged_decode);
+  m.def("paged_verify", &paged_verify);
   m.def("paged_prefill", &paged_prefill);
   m.def("kv_dequant_gather", &kv_dequant_gather);
   m.def("moe_gemm8_mxfp4", &moe_gemm8_mxfp4);

@@ -9,6 +9,7 @@ void register_gbdt(py::module_& m);
 void register_fs_store(py::module_& m);
 void register_shm_ring(py::module_& m);
 void register_epp_score(py::module_& m);
+void register_ngram(py::module_& m);
 
 PYBIND11_MODULE(_rt, m) {
   m.doc() = "llmd_amd native host runtime";
@@ -18,4 +19,5 @@ PYBIND11_MODULE(_rt, m) {
   register_fs_store(m);
   register_shm_ring(m);
   register_epp_score(m);
+  register_ngram(m);
 }

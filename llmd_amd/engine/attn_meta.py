@@ -1,7 +1,7 @@
 """Per-step attention metadata for a mixed (decode + chunked-prefill) batch.
 
 Token layout of a step: all decode tokens first (one per decoding sequence),
-then the prefill chunks back to back. The decode part can be replayed from a
+then the verify rows of speculating sequences, then the prefill chunks back to back. The decode part can be replayed from a
 captured hipGraph (static buffers, fixed split plan); the prefill part is
 always eager.
 """
@@ -27,6 +27,17 @@ class AttnMeta:
     d_max_ctx: int = 0
     d_cascade: Optional[tuple] = None              # shared-prefix decode (ops.cascade_tensors)
     d_split_dev: Optional[torch.Tensor] = None     # [1] int32 keys per split, set per graph replay
+    # verify part (speculative decoding): rows [num_decode, num_decode + num_verify), each
+    # sequence's last real token followed by its drafts; always eager
+    num_verify: int = 0                            # token rows
+    v_block_tables: Optional[torch.Tensor] = None  # [Bv, W] int32
+    v_seq_lens: Optional[torch.Tensor] = None      # [Bv] int32 context of each sequence's last row
+    v_q_start: Optional[torch.Tensor] = None       # [Bv] int32 (relative to the verify part)
+    v_q_len: Optional[torch.Tensor] = None         # [Bv] int32 rows per sequence (1 + drafts)
+    v_split: Optional[tuple] = None                # (split_size, nsplit)
+    v_workspace: Optional[tuple] = None            # (part_o, part_ml)
+    v_max_q: int = 0
+    v_max_ctx: int = 0
     # prefill part
     num_prefill_tokens: int = 0
     p_block_tables: Optional[torch.Tensor] = None  # [Bp, W] int32

@@ -369,6 +369,8 @@ class EngineConfig:
     lora_modules: Optional[dict] = None  # name -> adapter dir, loaded at start-up
     # structured outputs: DFA states the device arena of compiled grammars holds (513 B each)
     guided_arena_states: int = 32768
+    # speculative decoding (engine/spec_decode.py): vLLM's --speculative-config JSON, method "ngram" only
+    speculative_config: Optional[dict] = None
 
     @property
     def served_name(self) -> str:
@@ -393,6 +395,10 @@ class EngineConfig:
         if cfg.sched.prefill_token_align < 0:
             cfg.sched.prefill_token_align = (int(os.environ.get("LLMD_PREFILL_ALIGN", "512"))
                                              if str(cfg.device).startswith("cuda") else 0)
+        if cfg.speculative_config:
+            from .spec_decode import SpeculativeConfig
+
+            SpeculativeConfig.from_dict(cfg.speculative_config)  # ValueError: unsupported method / range
         return cfg
 
 
@@ -442,6 +448,9 @@ def add_engine_args(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
     p.add_argument("--kv-transfer-config", type=_json_arg, default=None)
     p.add_argument("--kv-events-config", type=_json_arg, default=None)
     p.add_argument("--kv-offload-config", type=_json_arg, default=None)
+    p.add_argument("--speculative-config", type=_json_arg, default=None,
+                   help='speculative decoding, vLLM JSON: {"method": "ngram", "num_speculative_tokens": 1..7, '
+                        '"prompt_lookup_max": n, "prompt_lookup_min": n} (n-gram prompt lookup is the only method)')
     p.add_argument("--scheduling-policy", default="fcfs", choices=["fcfs", "priority"])
     p.add_argument("--prefill-token-align", type=int, default=-1,
                    help="trim prefill-carrying steps to a multiple of this many tokens (GEMM M); "
@@ -538,6 +547,7 @@ def engine_config_from_args(a) -> EngineConfig:
         dbo_prefill_token_threshold=getattr(a, "dbo_prefill_token_threshold", 32),
         enforce_eager=eager, kv_transfer_config=a.kv_transfer_config,
         kv_events_config=a.kv_events_config, kv_offload_config=a.kv_offload_config,
+        speculative_config=getattr(a, "speculative_config", None),
         policy=a.scheduling_policy, prefill_token_align=getattr(a, "prefill_token_align", -1),
         async_scheduling=getattr(a, "async_scheduling", True),
         enable_lora=getattr(a, "enable_lora", False),

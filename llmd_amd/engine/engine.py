@@ -42,6 +42,11 @@ class LLMEngine:
     def __init__(self, cfg: EngineConfig, metrics: Optional[EngineMetrics] = None,
                  runner: Optional[ModelRunner] = None, capture_graphs: bool = True):
         self.cfg = cfg
+        from .spec_decode import SpecDecode, SpeculativeConfig
+
+        spec_cfg = SpeculativeConfig.from_dict(cfg.speculative_config)
+        if spec_cfg is not None:
+            self._check_spec_config(cfg)
         self.runner = runner or ModelRunner(cfg)
         nb = self.runner.profile_and_allocate() if self.runner.kv is None else self.runner.num_blocks
         rt = _rt_loader.rt()
@@ -62,6 +67,12 @@ class LLMEngine:
             self.connector = make_connector(cfg, self)
         self.sched = Scheduler(cfg, self.bm, self.connector)
         self.sched.on_guided_finish = self._guided_finish
+        # speculative decoding (engine/spec_decode.py): None unless --speculative-config is given;
+        # ``self.spec.proposer`` may be replaced by any callable(request, k) -> list[int]
+        self.spec = None
+        if spec_cfg is not None:
+            self._check_spec_runner()
+            self.spec = self.sched.spec = SpecDecode(spec_cfg)
         self.metrics = metrics or EngineMetrics(cfg.served_name, cfg.cache.block_size, nb,
                                                 max_lora=cfg.max_loras if cfg.enable_lora else 0)
         self.event_sink = None  # set by serving.kv_events.KVEventPublisher
@@ -95,8 +106,12 @@ class LLMEngine:
         self.last_num_tokens = 0
         # async scheduling: the launched step whose tokens are still on the device
         self._pending = None  # (SchedulerOutput, DeferredSample, t0)
+        # (speculation: the proposer reads token values, like penalties do - steps run synchronously)
         self.async_sched = bool(cfg.sched.async_scheduling and not self.dp_lockstep and self.runner.tp_size == 1
-                                and self.connector is None)
+                                and self.connector is None and self.spec is None)
+        if self.spec is not None and self.dp_lockstep:
+            raise ValueError("speculative decoding is not supported with DP-lockstep (wide-EP) engines: "
+                             "every rank must run the same kind of step")
 
     # ------------------------------------------------------------ API
     def add_request(self, request_id: str, prompt_token_ids: list[int],
@@ -121,6 +136,32 @@ class LLMEngine:
             raise
         self.metrics.on_arrival(r)
         return r
+
+    # ------------------------------------------------------------ speculative decoding
+    @staticmethod
+    def _check_spec_config(cfg: EngineConfig) -> None:
+        """What --speculative-config cannot be combined with, from the configuration alone."""
+        pc = cfg.parallel
+        if pc.tensor_parallel_size > 1:
+            raise ValueError("speculative decoding is not supported with tensor parallelism (TP > 1): "
+                             "TP followers replay plans without verify rows")
+        if pc.data_parallel_size > 1 or pc.enable_expert_parallel or pc.enable_dbo:
+            raise ValueError("speculative decoding is not supported with data parallelism / wide-EP / "
+                             "dual-batch overlap: every rank must run the same kind of step")
+        if cfg.kv_transfer_config:
+            raise ValueError("speculative decoding is not supported with a KV connector (P/D disaggregation)")
+        if cfg.model_config.kv_lora_rank:
+            raise ValueError("speculative decoding is not supported for MLA models: there is no "
+                             "multi-token verify kernel for the latent cache")
+
+    def _check_spec_runner(self) -> None:
+        if self.runner.is_mla:
+            raise ValueError("speculative decoding is not supported for MLA models")
+        if self.runner.hybrid:
+            raise ValueError("speculative decoding is not supported with the hybrid KV-cache manager "
+                             "(a separate sliding-window pool); pass --disable-hybrid-kv-cache-manager")
+        if self.runner.Hq // self.runner.Hkv > 16:
+            raise ValueError("speculative decoding needs at most 16 query heads per KV head")
 
     # ------------------------------------------------------------ structured outputs
     def set_token_table(self, table) -> None:
@@ -362,11 +403,12 @@ class LLMEngine:
         self.step_count += 1
         outs = err_outs
         for r in touched:
-            o = RequestOutput(r.request_id, [r.output_token_ids[-1]], [r.output_logprobs[-1]],
+            n = r.step_new_tokens  # 1; a verify step emits its accepted drafts and one more token
+            o = RequestOutput(r.request_id, r.output_token_ids[-n:], r.output_logprobs[-n:],
                               r.status.finished, r.finish_reason, r.num_prompt_tokens,
                               len(r.output_token_ids), r.num_cached_tokens)
             if r.params.top_logprobs:
-                o.new_top_logprobs = [r.output_top_logprobs[-1]]
+                o.new_top_logprobs = r.output_top_logprobs[-n:]
             if r.status.finished:
                 o.kv_transfer_params = r.extra.get("kv_transfer_params_out")
                 o.embedding = r.extra.get("embedding")
@@ -374,6 +416,8 @@ class LLMEngine:
             outs.append(o)
         self.metrics.on_step(so, touched, dt, self.sched.num_running, self.sched.num_waiting,
                              self.bm.usage(), self.bm.prefix_stats())
+        if self.spec is not None:
+            self.metrics.on_spec(self.spec)
         self._flush_events()
         return outs
 

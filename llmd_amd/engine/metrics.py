@@ -69,6 +69,15 @@ class EngineMetrics:
                                  buckets=TOK_BUCKETS, registry=r)
         self.iter_tokens = Histogram("vllm:iteration_tokens_total", "Tokens per engine step", L,
                                      buckets=TOK_BUCKETS, registry=r)
+        # speculative decoding (vLLM names); zero unless --speculative-config is given
+        self.spec_drafts = Counter("vllm:spec_decode_num_drafts", "Number of spec decoding drafts", L, registry=r)
+        self.spec_draft_tokens = Counter("vllm:spec_decode_num_draft_tokens", "Number of draft tokens", L,
+                                         registry=r)
+        self.spec_accepted = Counter("vllm:spec_decode_num_accepted_tokens", "Number of accepted tokens", L,
+                                     registry=r)
+        self.spec_accepted_pos = Counter("vllm:spec_decode_num_accepted_tokens_per_pos",
+                                         "Accepted tokens per draft position", L + ["position"], registry=r)
+        self._last_spec = (0, 0, 0, [])
         self._last_prefix = (0, 0)
         self._last_preempt = 0
         # in-process summaries for benchmarks (bounded: a long-running server must not grow them forever)
@@ -119,7 +128,7 @@ class EngineMetrics:
             self.prompt_tokens.labels(m).inc(ptoks)
             self.n_prompt += ptoks
         self._c_iter.observe(so.num_tokens)
-        ng = len(touched)
+        ng = sum(r.step_new_tokens for r in touched)
         if ng:
             self._c_gen.inc(ng)
             self.n_gen += ng
@@ -136,6 +145,23 @@ class EngineMetrics:
                     itl.observe(now - last)
                     self.itls.append(now - last)
             last_tok[r.request_id] = now
+
+    def on_spec(self, spec):
+        """Counters of engine/spec_decode.py SpecDecode -> the vllm:spec_decode_* series."""
+        m = self.model
+        d0, t0, a0, p0 = self._last_spec
+        if spec.num_drafts == d0:
+            return
+        self.spec_drafts.labels(m).inc(spec.num_drafts - d0)
+        self.spec_draft_tokens.labels(m).inc(spec.num_draft_tokens - t0)
+        if spec.num_accepted_tokens > a0:
+            self.spec_accepted.labels(m).inc(spec.num_accepted_tokens - a0)
+        for j, v in enumerate(spec.accepted_per_pos):
+            old = p0[j] if j < len(p0) else 0
+            if v > old:
+                self.spec_accepted_pos.labels(m, str(j)).inc(v - old)
+        self._last_spec = (spec.num_drafts, spec.num_draft_tokens, spec.num_accepted_tokens,
+                           list(spec.accepted_per_pos))
 
     def on_finish(self, r):
         m = self.model

@@ -91,10 +91,23 @@ class DeferredSample:
 
 def _host_samples(ids, lp, top, seq_ids) -> dict:
     """seq_id -> (token, logprob), or (token, logprob, [(token id, logprob), ...]) for the rows
-    that asked for alternatives (``top``: ids, logprobs, per-row counts; unused slots are -1)."""
+    that asked for alternatives (``top``: ids, logprobs, per-row counts; unused slots are -1).
+    A sequence with several rows (a speculative-decoding verify: consecutive, in position order)
+    maps to the list of its rows' (token, logprob)."""
     ids_h = ids.tolist()
     lp_h = lp.tolist() if lp is not None else [0.0] * len(ids_h)
     out = {s: (int(ids_h[i]), float(lp_h[i])) for i, s in enumerate(seq_ids)}
+    if len(out) < len(seq_ids):
+        out = {}
+        for i, s in enumerate(seq_ids):
+            out.setdefault(s, []).append((int(ids_h[i]), float(lp_h[i])))
+        out = {s: v if len(v) > 1 else v[0] for s, v in out.items()}
+        if top is not None:  # rows with alternatives are never verify rows
+            t_ids, t_lp, t_n = top[0].tolist(), top[1].tolist(), top[2]
+            for i, s in enumerate(seq_ids):
+                if t_n[i] > 0:
+                    out[s] += ([(t, l) for t, l in zip(t_ids[i][:t_n[i]], t_lp[i][:t_n[i]]) if t >= 0],)
+        return out
     if top is not None:
         t_ids, t_lp, t_n = top[0].tolist(), top[1].tolist(), top[2]
         for i, s in enumerate(seq_ids):
@@ -446,6 +459,8 @@ class ModelRunner:
             slots.append(bt[p // bs] * bs + p % bs)
             d_bt[i, : len(bt)] = bt
             d_len[i] = p + 1
+        # the last real token + the drafts of each verifying request
+        ver = self._prepare_verifies(so.verifies, block_tables, ids, pos, slots) if so.verifies else None
         p_ql, p_ctx = [], []
         p_bt = np.zeros((len(pre), self.width), dtype=np.int32)
         for i, sr in enumerate(pre):
@@ -460,7 +475,29 @@ class ModelRunner:
             p_bt[i, : len(bt)] = bt
             p_ql.append(sr.num_new_tokens)
             p_ctx.append(sr.start + sr.num_new_tokens)
-        return ids, pos, slots, d_bt, d_len, p_ql, p_ctx, p_bt
+        return ids, pos, slots, d_bt, d_len, p_ql, p_ctx, p_bt, ver
+
+    def _prepare_verifies(self, ver, block_tables, ids, pos, slots):
+        """Appends the verify rows (positions N-1 .. N-1+k of a request with N tokens) to the step's
+        token lists; returns (block tables, context of each last row, rows per request)."""
+        bs = self.bs
+        v_bt = np.zeros((len(ver), self.width), dtype=np.int32)
+        v_len = np.zeros(len(ver), dtype=np.int32)
+        v_ql = np.zeros(len(ver), dtype=np.int32)
+        for i, sr in enumerate(ver):
+            r = sr.req
+            bt = block_tables[r.seq_id]
+            n = sr.num_new_tokens
+            ids.append(r.token_at(sr.start))
+            ids.extend(sr.drafts)
+            ps = np.arange(sr.start, sr.start + n)
+            pos.extend(ps.tolist())
+            bta = np.asarray(bt, dtype=np.int64)
+            slots.extend((bta[ps // bs] * bs + ps % bs).tolist())
+            v_bt[i, : len(bt)] = bt
+            v_len[i] = sr.start + n
+            v_ql[i] = n
+        return v_bt, v_len, v_ql
 
     def _group_tables(self, so: SchedulerOutput, tables: dict):
         """Slot mapping and block tables of one KV group (the windowed pool of a
@@ -490,6 +527,10 @@ class ModelRunner:
                 rows.append(i)
                 reqs.append(sr.req)
         off = len(so.decodes)
+        for sr in so.verifies:  # every row of a verify is sampled: row j decides draft j
+            rows.extend(range(off, off + sr.num_new_tokens))
+            reqs.extend([sr.req] * sr.num_new_tokens)
+            off += sr.num_new_tokens
         for sr in so.prefills:
             off += sr.num_new_tokens
             if sr.samples:
@@ -504,14 +545,19 @@ class ModelRunner:
         topk = np.zeros(n, dtype=np.int32)
         topp = np.ones(n, dtype=np.float32)
         any_rand = any_k = any_p = False
+        prev, j = None, 0
         for i, r in enumerate(reqs):
             sp = r.params
+            # row j of a verify (the same request on consecutive rows) samples the token of output
+            # length len + j: it gets the seed plain decoding would use there
+            j = j + 1 if r is prev else 0
+            prev = r
             if sp.temperature > 0:
                 any_rand = True
                 temps[i] = sp.temperature
                 base = sp.seed if sp.seed is not None else r.extra.setdefault(
                     "_seed", int(self._rng.integers(0, 2**62)))
-                seeds[i] = _mix64(base * 1000003 + len(r.output_token_ids))
+                seeds[i] = _mix64(base * 1000003 + len(r.output_token_ids) + j)
             if sp.top_k > 0:
                 topk[i] = sp.top_k
                 any_k = True
@@ -580,15 +626,18 @@ class ModelRunner:
         """Host-side step description: everything a (TP) rank needs to run the
         forward, independent of the scheduler's request objects."""
         rows, reqs = self._sample_rows(so)
-        ids, pos, slots, d_bt, d_len, p_ql, p_ctx, p_bt = self._prepare(so, block_tables)
-        graph = not so.prefills and self._graph_ok(len(so.decodes))
+        ids, pos, slots, d_bt, d_len, p_ql, p_ctx, p_bt, ver = self._prepare(so, block_tables)
+        # a step with verify rows runs eager: the hipGraph buckets are decode-only
+        graph = not so.prefills and not so.verifies and self._graph_ok(len(so.decodes))
         pl = {"graph": graph, "nd": len(so.decodes), "ids": ids, "pos": pos, "slots": slots, "d_bt": d_bt,
               "d_len": d_len, "p_ql": p_ql, "p_ctx": p_ctx, "p_bt": p_bt, "rows": rows}
+        if ver is not None:
+            pl["verify"] = ver
         if self.hybrid:
             pl["swa"] = self._group_tables(so, block_tables.swa)
         if self.lora is not None:
             lo = [sr.req.lora_id for sr in so.decodes]
-            for sr in so.prefills:
+            for sr in so.verifies + so.prefills:
                 lo.extend([sr.req.lora_id] * sr.num_new_tokens)
             pl["lora"] = lo
         mm = self._mm_rows(so)
@@ -606,7 +655,7 @@ class ModelRunner:
         from llmd_amd.models.vision import chunk_mm_rows
 
         rows, embs = [], []
-        row0 = len(so.decodes)
+        row0 = len(so.decodes) + so.num_verify_tokens
         for sr in so.prefills:
             if sr.req.mm_inputs:
                 r, e = chunk_mm_rows(sr.req.mm_inputs, sr.start, sr.num_new_tokens, row0)
@@ -786,6 +835,23 @@ class ModelRunner:
                 # splits cover the longest own suffix (and a windowed layer's window)
                 mctx = max(int((d_len - plan.sstart[:nd]).max()), min(self.max_window, mctx))
             meta.d_split = ops.decode_split_plan(mctx, nd, self.Hkv, self.Hq // self.Hkv)
+        if pl.get("verify") is not None:
+            v_bt, v_len, v_ql = pl["verify"]
+            meta.num_verify = int(v_ql.sum())
+            meta.v_block_tables = torch.from_numpy(v_bt).to(dev, non_blocking=True)
+            meta.v_seq_lens = torch.from_numpy(v_len).to(dev, non_blocking=True)
+            meta.v_q_len = torch.from_numpy(v_ql).to(dev, non_blocking=True)
+            meta.v_q_start = torch.from_numpy((np.cumsum(v_ql) - v_ql).astype(np.int32)).to(dev, non_blocking=True)
+            meta.v_max_q = int(v_ql.max())
+            meta.v_max_ctx = int(v_len.max())
+            if self.is_gpu:
+                G = self.Hq // self.Hkv
+                meta.v_split = ops.verify_split_plan(meta.v_max_ctx, len(v_ql), self.Hkv, G, meta.v_max_q, 0,
+                                                     self.D, self.kv_dtype == torch.float8_e4m3fn)
+                if meta.v_split[1] > 1:  # one workspace for every layer of the step
+                    n = meta.num_verify * self.Hq * meta.v_split[1]
+                    meta.v_workspace = (torch.empty(n * self.D, dtype=torch.float32, device=dev),
+                                        torch.empty(n * 2, dtype=torch.float32, device=dev))
         if p_ql:
             meta.num_prefill_tokens = sum(p_ql)
             meta.p_block_tables = torch.from_numpy(p_bt).to(dev, non_blocking=True)

@@ -187,6 +187,8 @@ class Request:
     # structured outputs: the DFA state of params.guided after the output tokens so far (1 = start);
     # it moves only where a real token is written, never on an async placeholder
     guided_state: int = 1
+    # output tokens the last step appended (speculative decoding: 1 + the accepted drafts)
+    step_new_tokens: int = 1
 
     @property
     def cache_extra(self) -> int:

@@ -41,6 +41,9 @@ class ScheduledReq:
     req: Request
     num_new_tokens: int
     start: int  # num_computed_tokens before this step
+    # speculative decoding: draft tokens verified after the request's last real token
+    # (num_new_tokens = 1 + len(drafts)); empty for every other entry
+    drafts: list = ()
 
     @property
     def is_decode(self) -> bool:
@@ -56,17 +59,24 @@ class SchedulerOutput:
     decodes: list[ScheduledReq] = field(default_factory=list)
     prefills: list[ScheduledReq] = field(default_factory=list)
     preempted: list[Request] = field(default_factory=list)
+    # speculative decoding: running requests that verify drafts this step. Token layout of a
+    # step: decodes | verifies | prefills
+    verifies: list[ScheduledReq] = field(default_factory=list)
+
+    @property
+    def num_verify_tokens(self) -> int:
+        return sum(s.num_new_tokens for s in self.verifies)
 
     @property
     def num_tokens(self) -> int:
-        return len(self.decodes) + sum(s.num_new_tokens for s in self.prefills)
+        return len(self.decodes) + self.num_verify_tokens + sum(s.num_new_tokens for s in self.prefills)
 
     @property
     def empty(self) -> bool:
-        return not self.decodes and not self.prefills
+        return not self.decodes and not self.prefills and not self.verifies
 
     def all(self) -> list[ScheduledReq]:
-        return self.decodes + self.prefills
+        return self.decodes + self.verifies + self.prefills
 
 
 class _WaitQueue:
@@ -147,6 +157,8 @@ class Scheduler:
         # a finished constrained request (its grammar is no longer pinned in the device arena)
         self.token_table = None
         self.on_guided_finish = None
+        # speculative decoding (set by the engine): engine/spec_decode.py SpecDecode, or None
+        self.spec = None
 
     # ------------------------------------------------------------ admission
     def add_request(self, req: Request):
@@ -209,11 +221,13 @@ class Scheduler:
         victim.num_preemptions += 1
         victim.status = Status.PREEMPTED
         self.num_preemptions_total += 1
+        if self.spec is not None:
+            self.spec.drop(victim)  # recompute rebuilds its n-gram index
         self.waiting.push(victim, front=True)
         out.preempted.append(victim)
 
     def _unschedule(self, victim: Request, out: SchedulerOutput) -> int:
-        for lst in (out.decodes, out.prefills):
+        for lst in (out.decodes, out.verifies, out.prefills):
             for k, sr in enumerate(lst):
                 if sr.req is victim:
                     lst.pop(k)
@@ -289,6 +303,11 @@ class Scheduler:
             n = min(n, budget)
             if self.sc.long_prefill_token_threshold and n > 1:
                 n = min(n, self.sc.long_prefill_token_threshold)
+            drafts = self._propose(r, budget) if (self.spec is not None and n == 1) else ()
+            if drafts and self.bm.grow(r.seq_id, r.num_computed_tokens + 1 + len(drafts)):
+                n = 1 + len(drafts)  # a verify counts against the budget like a chunk and is never trimmed
+            else:
+                drafts = ()  # no room for the drafts' KV: a plain decode row, before preempting anyone
             self_preempted = False
             while not self.bm.grow(r.seq_id, r.num_computed_tokens + n):
                 victim = self._pick_victim()
@@ -302,8 +321,8 @@ class Scheduler:
                     i -= 1
             if self_preempted:
                 continue  # r left `running`; index i now points at the next request
-            sr = ScheduledReq(r, n, r.num_computed_tokens)
-            (out.decodes if sr.is_decode else out.prefills).append(sr)
+            sr = ScheduledReq(r, n, r.num_computed_tokens, drafts)
+            (out.verifies if drafts else out.decodes if sr.is_decode else out.prefills).append(sr)
             budget -= n
             i += 1
         # 2. waiting
@@ -377,6 +396,21 @@ class Scheduler:
         self._align_tokens(out)
         return out
 
+    def _propose(self, r: Request, budget: int) -> list:
+        """Draft tokens for a running request with one token left to compute, or (): it must be
+        sampled by the plain path (no penalties, constraint, alternatives or embedding), and the
+        drafts fit max_tokens, max_model_len and the step's token budget."""
+        p = r.params
+        if r.num_tokens - r.num_computed_tokens != 1:  # a chunk cut to one token by the budget
+            return ()
+        if p.penalized or p.constrained or p.embed or p.top_logprobs or r.final_pending or r.async_pending:
+            return ()
+        k = min(self.spec.k, p.max_tokens - len(r.output_token_ids) - 1,
+                self.sc.max_model_len - r.num_tokens - 1, budget - 1)
+        if k <= 0:
+            return ()
+        return self.spec.propose(r, k)
+
     def _reload_cannot_fit(self, r, cached: int, budget: int) -> bool:
         """True when the pool cannot hold this request's first chunk even after a
         tier reload (the blocks it holds now plus the free ones): reloading host /
@@ -434,6 +468,10 @@ class Scheduler:
             r = sr.req
             if r.status.finished:
                 continue
+            if sr.drafts:
+                if self._update_verify(sr, sampled[r.seq_id], now, bs):
+                    touched.append(r)
+                continue
             r.num_computed_tokens = sr.start + sr.num_new_tokens
             # hash/register newly completed blocks only (a decode completes one
             # every block_size steps; converting the whole context each step cost
@@ -458,9 +496,42 @@ class Scheduler:
                 if r.first_token_time is None:
                     r.first_token_time = now
                 r.last_token_time = now
+                r.step_new_tokens = 1
                 self._check_stop(r)
                 touched.append(r)
         return touched
+
+    def _update_verify(self, sr: ScheduledReq, rows: list, now: float, bs: int) -> bool:
+        """A verify entry's step: ``rows`` are the 1 + k sampled (token, logprob) rows. The longest
+        prefix of drafts equal to the sampled tokens is accepted; the request emits the sampled
+        tokens up to and including the first one that differs (or the bonus token after a fully
+        accepted run), one at a time through the stop checks, so it ends where plain decoding ends."""
+        r, drafts = sr.req, sr.drafts
+        n_acc = 0
+        while n_acc < len(drafts) and rows[n_acc][0] == drafts[n_acc]:
+            n_acc += 1
+        self.spec.record(len(drafts), n_acc)
+        # computed: the last real token and the accepted drafts (their KV is in the cache; the
+        # rejected drafts' slots are overwritten by the next step)
+        r.num_computed_tokens = sr.start + 1 + n_acc
+        if (self.cfg.cache.enable_prefix_caching and r.num_computed_tokens // bs > sr.start // bs
+                and self.bm.has_seq(r.seq_id)):
+            # block hashes over real tokens only: the accepted drafts are the tokens sampled below
+            toks = np.concatenate([self._tokens(r), np.asarray(drafts[:n_acc], dtype=np.int32)])
+            self.bm.commit(r.seq_id, toks, r.num_computed_tokens)
+        n0 = len(r.output_token_ids)
+        for tok, lp, *_ in rows[:n_acc + 1]:
+            r.output_token_ids.append(tok)
+            r.output_logprobs.append(lp)
+            r.output_top_logprobs.append(None)
+            if r.first_token_time is None:
+                r.first_token_time = now
+            r.last_token_time = now
+            self._check_stop(r)
+            if r.status.finished:
+                break
+        r.step_new_tokens = len(r.output_token_ids) - n0
+        return True
 
     # ------------------------------------------------------------ async scheduling
     # A step's update split in two (engine.py async path): ``advance`` when the step is
@@ -552,6 +623,8 @@ class Scheduler:
     def _finish(self, r: Request, status: Status, free_blocks: bool = True):
         r.status = status
         r.finished_time = time.monotonic()
+        if self.spec is not None:
+            self.spec.drop(r)
         if r.params.guided is not None and self.on_guided_finish is not None:
             self.on_guided_finish(r)
         ktp = r.kv_transfer_params or {}

@@ -289,11 +289,18 @@ class PagedAttention(torch.nn.Module):
                                  split=meta.d_split, out=out[:nd], workspace=meta.d_workspace,
                                  max_ctx=meta.d_max_ctx, k_scale=self.k_scale, v_scale=self.v_scale,
                                  cascade=meta.d_cascade, split_dev=meta.d_split_dev)
+        nv = meta.num_verify
+        if nv:  # speculative decoding: the drafts' K/V were written above with the rest of the step
+            ops.paged_verify(qkv[nd:nd + nv], self.k_cache, self.v_cache, meta.v_block_tables,
+                             meta.v_seq_lens, meta.v_q_start, meta.v_q_len, Hq, Hkv, D, self.scale,
+                             self.window, self.sinks, split=meta.v_split, out=out[nd:nd + nv],
+                             workspace=meta.v_workspace, max_ctx=meta.v_max_ctx, k_scale=self.k_scale,
+                             v_scale=self.v_scale, max_q=meta.v_max_q)
         if meta.num_prefill_tokens:
             items = meta.p_items
-            ops.paged_prefill(qkv[nd:], self.k_cache, self.v_cache, meta.p_block_tables,
+            ops.paged_prefill(qkv[nd + nv:], self.k_cache, self.v_cache, meta.p_block_tables,
                               meta.p_q_start, meta.p_q_len, meta.p_ctx_len, Hq, Hkv, D, self.scale,
-                              self.window, self.sinks, items=items, out=out[nd:], k_scale=self.k_scale,
+                              self.window, self.sinks, items=items, out=out[nd + nv:], k_scale=self.k_scale,
                               v_scale=self.v_scale)
         if side is not None:
             torch.cuda.current_stream(qkv.device).wait_stream(side)

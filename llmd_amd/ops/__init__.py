@@ -375,6 +375,88 @@ def paged_decode(q, k_cache, v_cache, block_tables, seq_lens, Hq, Hkv, D, scale,
     return out
 
 
+VERIFY_MAX_Q = 8  # query tokens per sequence of paged_verify: 1 + at most 7 drafts
+
+
+_VERIFY_NP = int(os.environ.get("LLMD_VERIFY_NP", "0"))  # 1 | 2 forces the passes per workgroup (A/B)
+
+
+def verify_passes(cols: int, D: int, fp8: bool, window: int = 0) -> int:
+    """16-column passes per workgroup of paged_verify for ``cols`` = q_len x G query columns; the
+    other column groups go on the grid and find the K/V in L2. Measured at batch 64, context 5000
+    (profiles/spec_verify_attn.txt): two passes at D 128 leave one wave per SIMD and run a bf16 group
+    at 2.2x the time of one pass (475 vs 221 us), so bf16 D 128 always takes one; an fp8 cache (half
+    the K/V registers) gains from two passes when that halves the number of groups; bf16 D 64 keeps
+    two waves per SIMD with two passes (115 vs 186 us at 24 columns); over a sliding window the
+    workgroups are short and more of them cost less than a second pass, past two groups."""
+    groups = -(-cols // 16)
+    if _VERIFY_NP in (1, 2):
+        return _VERIFY_NP
+    if groups == 1:
+        return 1
+    if window and window > 0:
+        return 2 if groups == 2 else 1
+    if not fp8:
+        return 1 if D == 128 else 2
+    return 2 if groups % 2 == 0 else 1
+
+
+def verify_split_plan(max_ctx: int, batch: int, Hkv: int, G: int, max_q: int, window: int = 0,
+                      D: int = 128, fp8: bool = False):
+    """(split_size, nsplit) for paged_verify: the decode plan over the key range the kernel walks (a
+    window's union over the tokens is window + max_q - 1 keys) with its workgroups per split."""
+    if window and window > 0:
+        max_ctx = min(max_ctx, window + max_q - 1)
+    cols = max_q * G
+    ncg = -(-cols // (16 * verify_passes(cols, D, fp8, window)))
+    return decode_split_plan(max_ctx, batch * ncg, Hkv, 1)
+
+
+def paged_verify(q, k_cache, v_cache, block_tables, seq_lens, q_start, q_len, Hq, Hkv, D, scale, window=0,
+                 sinks=None, split=None, out=None, workspace=None, max_ctx=None, k_scale=1.0, v_scale=1.0,
+                 max_q=None):
+    """Attention of speculative-decoding verify rows: q [T, >=Hq*D] -> out [T, Hq*D]. Sequence b owns
+    rows q_start[b] .. q_start[b] + q_len[b] (its newest 1 <= q_len <= 8 tokens, drafts included, whose
+    K/V the cache already holds); seq_lens[b] is the context of its last row, and row j sees the keys
+    a decode row at that position would. One kernel pass reads the sequence's K/V once for all rows.
+    max_q: the largest q_len (sizes the grid; read from q_len, with a device sync, when not given).
+    The workspace holds nsplit slots per (row of q, head)."""
+    G = Hq // Hkv
+    if G > 16:
+        raise ValueError(f"paged_verify: {G} query heads per KV head (at most 16)")
+    T, B = q.shape[0], seq_lens.shape[0]
+    if max_q is None:
+        max_q = int(q_len.max().item()) if B else 1
+    if max_q > VERIFY_MAX_Q:
+        raise ValueError(f"paged_verify: q_len {max_q} above {VERIFY_MAX_Q}")
+    if not _gpu(q):
+        r = ref.paged_prefill(q, k_cache, v_cache, block_tables, q_start, q_len, seq_lens, Hq, Hkv, D,
+                              scale, window, sinks, k_scale, v_scale)
+        if out is not None:
+            out.copy_(r)
+            return out
+        return r
+    if out is None:
+        out = torch.empty(T, Hq * D, dtype=q.dtype, device=q.device)
+    fp8 = k_cache.dtype == torch.float8_e4m3fn
+    if split is None:
+        if max_ctx is None:
+            max_ctx = int(seq_lens.max().item()) if B else 1
+        split = verify_split_plan(max_ctx, B, Hkv, G, max_q, window, D, fp8)
+    split_size, nsplit = split
+    if nsplit > 1:
+        if workspace is None:
+            part_o = torch.empty(T * Hq * nsplit * D, dtype=torch.float32, device=q.device)
+            part_ml = torch.empty(T * Hq * nsplit * 2, dtype=torch.float32, device=q.device)
+        else:
+            part_o, part_ml = workspace
+    else:
+        part_o = part_ml = out.new_empty(0, dtype=torch.float32)
+    native().paged_verify(out, q, k_cache, v_cache, block_tables, seq_lens, q_start, q_len, max_q,
+                          verify_passes(max_q * G, D, fp8, window), Hq, Hkv, D, scale, window, sinks, split_size, nsplit, part_o, part_ml, k_scale, v_scale)
+    return out
+
+
 def build_prefill_items(q_len: list[int], ctx_len: list[int], tpi: int) -> list[tuple[int, int]]:
     """Work items (seq, first q token), heaviest (most keys) first."""
     items = []
