@@ -42,6 +42,8 @@ void llmd_topk_topp_mask(float*, int64_t, int, int, const int*, const float*, co
                          hipStream_t);
 void llmd_top_logprobs(const void*, int64_t, int, int, int, const int*, int, int*, float*, hipStream_t);
 int llmd_top_logprobs_max();
+void llmd_prompt_logprobs(const void*, int64_t, int, int, int, const int*, const int*, int, float*, int*, int*, float*,
+                          hipStream_t);
 void llmd_guided_mask(void*, int64_t, int, int, int, const uint16_t*, const uint8_t*, int, const int*, const int*,
                       const int*, const uint8_t*, int64_t, const int*, const int*, int, hipStream_t);
 int llmd_guided_lds_states();
@@ -816,6 +818,41 @@ void top_logprobs(torch::Tensor logits, torch::Tensor n_per_row, torch::Tensor o
                     out_ids.data_ptr<int>(), out_lp.data_ptr<float>(), cur_stream());
 }
 
+// prompt scoring: row r against targets[r] (int32 [R]): out_lp f32 [R], out_rank int32 [R], and the
+// n_per_row[r] alternatives of top_logprobs in out_ids / out_top_lp [R, llmd_top_logprobs_max()]
+void prompt_logprobs(torch::Tensor logits, torch::Tensor targets, torch::Tensor n_per_row, torch::Tensor out_lp,
+                     torch::Tensor out_rank, torch::Tensor out_ids, torch::Tensor out_top_lp) {
+  const c10::hip::OptionalHIPGuard device_guard(dev_of(logits));
+  CHECK_CUDA(logits); CHECK_INNER(logits);
+  TORCH_CHECK(logits.dim() == 2, "logits 2-D");
+  const bool bf = logits.scalar_type() == at::kBFloat16;
+  TORCH_CHECK(bf || logits.scalar_type() == at::kFloat, "logits bf16/f32");
+  const int64_t R = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(V < (int64_t)1 << 31 && R < (int64_t)1 << 31, "logits too large");
+  TORCH_CHECK(logits.stride(0) % (bf ? 8 : 4) == 0 && (uintptr_t)logits.data_ptr() % 16 == 0,
+              "16-B aligned logits rows");
+  const int nmax = llmd_top_logprobs_max();
+  CHECK_CUDA(targets); CHECK_DT(targets, at::kInt);
+  CHECK_CUDA(n_per_row); CHECK_DT(n_per_row, at::kInt);
+  CHECK_CUDA(out_lp); CHECK_DT(out_lp, at::kFloat);
+  CHECK_CUDA(out_rank); CHECK_DT(out_rank, at::kInt);
+  CHECK_CUDA(out_ids); CHECK_DT(out_ids, at::kInt);
+  CHECK_CUDA(out_top_lp); CHECK_DT(out_top_lp, at::kFloat);
+  for (const torch::Tensor* t : {&targets, &n_per_row, &out_lp, &out_rank, &out_ids, &out_top_lp})
+    TORCH_CHECK(t->is_contiguous() && t->device() == logits.device(),
+                "targets, n_per_row and outputs: contiguous, on the logits' device");
+  TORCH_CHECK(targets.dim() == 1 && targets.size(0) == R, "targets [R]");
+  TORCH_CHECK(n_per_row.dim() == 1 && n_per_row.size(0) == R, "n_per_row [R]");
+  TORCH_CHECK(out_lp.dim() == 1 && out_lp.size(0) == R, "out_lp [R]");
+  TORCH_CHECK(out_rank.dim() == 1 && out_rank.size(0) == R, "out_rank [R]");
+  TORCH_CHECK(out_ids.dim() == 2 && out_ids.size(0) == R && out_ids.size(1) == nmax, "out_ids [R, MAX_TOP_LOGPROBS]");
+  TORCH_CHECK(out_top_lp.dim() == 2 && out_top_lp.size(0) == R && out_top_lp.size(1) == nmax,
+              "out_top_lp [R, MAX_TOP_LOGPROBS]");
+  llmd_prompt_logprobs(logits.data_ptr(), logits.stride(0), (int)R, (int)V, bf ? 1 : 0, targets.data_ptr<int>(),
+                       n_per_row.data_ptr<int>(), nmax, out_lp.data_ptr<float>(), out_rank.data_ptr<int>(),
+                       out_ids.data_ptr<int>(), out_top_lp.data_ptr<float>(), cur_stream());
+}
+
 // guided-decoding mask in place (csrc/ops/guided.hip): trans uint16 [cap, 256] / accept uint8 [cap] the DFA
 // arena, dfa_off / dfa_n / state int32 [B] per row (state -1: row untouched), tok_bytes uint8 + tok_off int32
 // [V + 1] the token byte table. The per-row values are validated on the host by ops.guided_mask.
@@ -1413,6 +1450,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {  // _C, or _C_debug (llmd_amd/build.p
   m.def("topk_topp_mask", &topk_topp_mask);
   m.def("top_logprobs", &top_logprobs);
   m.def("top_logprobs_max", &llmd_top_logprobs_max);
+  m.def("prompt_logprobs", &prompt_logprobs);
   m.def("guided_mask", &guided_mask);
   m.def("guided_lds_states", &llmd_guided_lds_states);
   m.def("guided_splits", &llmd_guided_splits);

@@ -20,6 +20,9 @@
 // A row that sends more than CAP candidates (an order that follows the thread mapping)
 // takes n rounds of "largest comp below the previous one" over the row instead: slow
 // and exact.
+//
+// prompt_logprobs_kernel (prompt scoring) runs the same passes (row_top) for a row and a given
+// target token, and adds the target's log-probability and rank; see there.
 #include "llmd_common.h"
 
 using namespace llmd;
@@ -80,33 +83,26 @@ __device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
   return v;
 }
 
-template <bool BF16>
-__global__ __launch_bounds__(NT) void top_logprobs_kernel(const void* __restrict__ logits, int64_t stride, int V,
-                                                          const int* __restrict__ n_per_row,
-                                                          int* __restrict__ out_ids, float* __restrict__ out_lp) {
-  const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  int* oid = out_ids + (int64_t)row * NMAX;
-  float* olp = out_lp + (int64_t)row * NMAX;
-  const int n = min(max(n_per_row[row], 0), NMAX);
-  if (n == 0) {  // nothing asked of this row: its logits are not read
-    if (tid < NMAX) {
-      oid[tid] = -1;
-      olp[tid] = NEG_INF;
-    }
-    return;
-  }
-  const void* r = BF16 ? (const void*)((const uint16_t*)logits + (int64_t)row * stride)
-                       : (const void*)((const float*)logits + (int64_t)row * stride);
+// One row through pass 1 / pass 2 / select, by the whole workgroup: the n best entries to oid / olp
+// (unused slots -1 / -inf). SCORE: pass 1 also counts the entries >= xt (the vLLM rank of a
+// target whose stored value is xt), and a row with n == 0 stops after pass 1. logZ and the count
+// are returned in every thread.
+template <bool BF16, bool SCORE>
+__device__ __forceinline__ void row_top(const void* r, int V, int n, float xt, int* __restrict__ oid,
+                                        float* __restrict__ olp, float& logZ_out, int& count_out) {
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   __shared__ uint64_t s_grp[NW][64];
   __shared__ uint64_t s_cand[CAP];
   __shared__ float s_mx[NW], s_se[NW];
   __shared__ unsigned long long s_T, s_best;
   __shared__ uint32_t s_cnt;
+  // the per-wave counts of SCORE live in the candidate slots, which nobody writes before pass 2
+  int* s_ge = reinterpret_cast<int*>(s_cand);
 
   // ---- pass 1: max / sum-exp (sample_kernel's guards for masked entries) and the thread's best
   float mx = NEG_INF, se = 0.f;
   uint32_t bk = KEY_NEG_INF;
-  int bi = 0;
+  int bi = 0, ge = 0;
   for_each<BF16>(r, V, [&](float x, int i) {
     if (x > mx) {
       se = se * __expf(mx - x) + 1.f;
@@ -114,6 +110,7 @@ __global__ __launch_bounds__(NT) void top_logprobs_kernel(const void* __restrict
     } else if (x != NEG_INF) {
       se += __expf(x - mx);
     }
+    if (SCORE) ge += x >= xt;
     const uint32_t key = fkey(x);
     if (key > bk) {  // indices ascend: the first of equal keys stays
       bk = key;
@@ -126,10 +123,12 @@ __global__ __launch_bounds__(NT) void top_logprobs_kernel(const void* __restrict
     const float nm = fmaxf(mx, omx);
     se = (mx == NEG_INF ? 0.f : se * __expf(mx - nm)) + (omx == NEG_INF ? 0.f : ose * __expf(omx - nm));
     mx = nm;
+    if (SCORE) ge += __shfl_xor(ge, o, 64);
   }
   if (lane == 0) {
     s_mx[w] = mx;
     s_se[w] = se;
+    if (SCORE) s_ge[w] = ge;
   }
   s_grp[w][lane] = bk > KEY_NEG_INF ? comp_of(bk, bi) : 0ull;  // 0: no reportable entry
   if (tid == 0) {
@@ -145,6 +144,19 @@ __global__ __launch_bounds__(NT) void top_logprobs_kernel(const void* __restrict
     M = nm;
   }
   const float logZ = M + __logf(S);
+  logZ_out = logZ;
+  count_out = 0;
+  if (SCORE) {
+#pragma unroll
+    for (int k = 0; k < NW; ++k) count_out += s_ge[k];
+    if (n == 0) {  // the same in every thread: the row was read once
+      if (tid < NMAX) {
+        oid[tid] = -1;
+        olp[tid] = NEG_INF;
+      }
+      return;
+    }
+  }
   if (w == 0) {
     uint64_t g = 0ull;
 #pragma unroll
@@ -217,6 +229,60 @@ __global__ __launch_bounds__(NT) void top_logprobs_kernel(const void* __restrict
   }
 }
 
+template <bool BF16>
+__device__ __forceinline__ const void* row_ptr(const void* logits, int64_t stride, int row) {
+  return BF16 ? (const void*)((const uint16_t*)logits + (int64_t)row * stride)
+              : (const void*)((const float*)logits + (int64_t)row * stride);
+}
+
+template <bool BF16>
+__global__ __launch_bounds__(NT) void top_logprobs_kernel(const void* __restrict__ logits, int64_t stride, int V,
+                                                          const int* __restrict__ n_per_row,
+                                                          int* __restrict__ out_ids, float* __restrict__ out_lp) {
+  const int row = blockIdx.x, tid = threadIdx.x;
+  int* oid = out_ids + (int64_t)row * NMAX;
+  float* olp = out_lp + (int64_t)row * NMAX;
+  const int n = min(max(n_per_row[row], 0), NMAX);
+  if (n == 0) {  // nothing asked of this row: its logits are not read
+    if (tid < NMAX) {
+      oid[tid] = -1;
+      olp[tid] = NEG_INF;
+    }
+    return;
+  }
+  float logZ;
+  int count;
+  row_top<BF16, false>(row_ptr<BF16>(logits, stride, row), V, n, 0.f, oid, olp, logZ, count);
+}
+
+// Prompt scoring: row r against its target token t = targets[r].
+//   lp   = x[t] - logZ, logZ as in top_logprobs_kernel
+//   rank = number of entries with x[i] >= x[t] (vLLM: 1 is the best, ties with the target count),
+//          counted in pass 1, so a row with n_per_row == 0 is read once
+//   top  = what top_logprobs_kernel reports for the row and n_per_row[r] (the same row_top)
+// t outside [0, V): lp = -inf, rank = 0, and no entry is read for it. x[t] == -inf: lp = -inf, rank = V.
+template <bool BF16>
+__global__ __launch_bounds__(NT) void prompt_logprobs_kernel(const void* __restrict__ logits, int64_t stride, int V,
+                                                             const int* __restrict__ targets,
+                                                             const int* __restrict__ n_per_row,
+                                                             float* __restrict__ out_lp, int* __restrict__ out_rank,
+                                                             int* __restrict__ out_ids, float* __restrict__ out_tlp) {
+  const int row = blockIdx.x;
+  const int n = min(max(n_per_row[row], 0), NMAX);
+  const void* r = row_ptr<BF16>(logits, stride, row);
+  const int t = targets[row];
+  const bool in_row = t >= 0 && t < V;
+  float xt = 0.f;
+  if (in_row) xt = BF16 ? bf2f(((const uint16_t*)r)[t]) : ((const float*)r)[t];
+  float logZ;
+  int count;
+  row_top<BF16, true>(r, V, n, xt, out_ids + (int64_t)row * NMAX, out_tlp + (int64_t)row * NMAX, logZ, count);
+  if (threadIdx.x == 0) {
+    out_lp[row] = in_row && xt != NEG_INF ? xt - logZ : NEG_INF;
+    out_rank[row] = in_row ? count : 0;
+  }
+}
+
 }  // namespace
 
 extern "C" int llmd_top_logprobs_max() { return NMAX; }
@@ -231,4 +297,17 @@ extern "C" void llmd_top_logprobs(const void* logits, int64_t stride, int B, int
   else
     hipLaunchKernelGGL(top_logprobs_kernel<false>, dim3(B), dim3(NT), 0, st, logits, stride, V, n_per_row, out_ids,
                        out_lp);
+}
+
+// out_lp / out_rank: [R]; out_ids / out_tlp: [R, NMAX] with NMAX == llmd_top_logprobs_max()
+extern "C" void llmd_prompt_logprobs(const void* logits, int64_t stride, int R, int V, int is_bf16, const int* targets,
+                                     const int* n_per_row, int nmax, float* out_lp, int* out_rank, int* out_ids,
+                                     float* out_tlp, hipStream_t st) {
+  if (R == 0 || nmax != NMAX) return;
+  if (is_bf16)
+    hipLaunchKernelGGL(prompt_logprobs_kernel<true>, dim3(R), dim3(NT), 0, st, logits, stride, V, targets, n_per_row,
+                       out_lp, out_rank, out_ids, out_tlp);
+  else
+    hipLaunchKernelGGL(prompt_logprobs_kernel<false>, dim3(R), dim3(NT), 0, st, logits, stride, V, targets, n_per_row,
+                       out_lp, out_rank, out_ids, out_tlp);
 }

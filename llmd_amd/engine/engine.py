@@ -122,6 +122,9 @@ class LLMEngine:
             params.check_vocab(self.cfg.model_config.vocab_size)
         if params is not None and params.constrained:
             self._check_guided(params)
+        if params is not None and params.scored:
+            self.check_scored(params, kv_transfer_params, mm_inputs)
+            self.runner.scored_seen = True
         r = Request(request_id, list(prompt_token_ids), params or SamplingParams(), priority=priority,
                     kv_transfer_params=kv_transfer_params, lora_id=lora_id, mm_inputs=mm_inputs or None)
         if arrival_time is not None:
@@ -136,6 +139,30 @@ class LLMEngine:
             raise
         self.metrics.on_arrival(r)
         return r
+
+    # ------------------------------------------------------------ prompt scoring
+    def check_scored(self, params: SamplingParams, kv_transfer_params=None, mm_inputs=None) -> None:
+        """What a request with prompt_logprobs cannot be combined with (ValueError -> HTTP 400). The
+        scoring rows run on the driver after its own forward: ranks that replay a plan, exchange KV
+        or split the batch have no place for them. Reads configuration only (any thread may call)."""
+        pc = self.cfg.parallel
+        why = None
+        if pc.tensor_parallel_size > 1 or self.runner.tp_size > 1:
+            why = "tensor parallelism (TP > 1): TP followers replay plans without scoring rows"
+        elif self.dp_lockstep or pc.data_parallel_size > 1 or pc.enable_expert_parallel:
+            why = "DP-lockstep / wide-EP engines: every rank must run the same kind of step"
+        elif pc.enable_dbo:
+            why = "dual-batch overlap"
+        elif self.connector is not None or self.cfg.kv_transfer_config:
+            why = "a KV connector (P/D disaggregation): a transferred prompt is never computed here"
+        elif kv_transfer_params:
+            why = "kv_transfer_params on the request"
+        elif mm_inputs:
+            why = "multimodal inputs: image placeholder rows have no token to score"
+        elif params.embed:
+            why = "embedding requests"
+        if why is not None:
+            raise ValueError(f"prompt_logprobs / echo with logprobs is not supported with {why}")
 
     # ------------------------------------------------------------ speculative decoding
     @staticmethod
@@ -257,6 +284,9 @@ class LLMEngine:
             if r.params.penalized or r.params.embed or r.params.constrained \
                     or (r.async_pending and sr.start + sr.num_new_tokens >= r.num_tokens):
                 return True
+        if self.runner.scored_seen:
+            # prompt scoring copies its results to the host inside the step: it runs synchronously
+            return any(sr.req.params.scored and self.runner.score_rows(sr) for sr in so.decodes + so.prefills)
         return False
 
     def _step_async(self) -> list[RequestOutput]:
@@ -409,6 +439,8 @@ class LLMEngine:
                               len(r.output_token_ids), r.num_cached_tokens)
             if r.params.top_logprobs:
                 o.new_top_logprobs = r.output_top_logprobs[-n:]
+            if r.params.scored and len(r.output_token_ids) == n:  # once: with the first generated token
+                o.prompt_logprobs = r.prompt_logprobs
             if r.status.finished:
                 o.kv_transfer_params = r.extra.get("kv_transfer_params_out")
                 o.embedding = r.extra.get("embedding")
@@ -418,6 +450,8 @@ class LLMEngine:
                              self.bm.usage(), self.bm.prefix_stats())
         if self.spec is not None:
             self.metrics.on_spec(self.spec)
+        if self.runner.num_scored:
+            self.metrics.on_scored(self.runner.num_scored)
         self._flush_events()
         return outs
 

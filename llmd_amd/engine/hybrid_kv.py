@@ -60,8 +60,11 @@ class HybridBlockManager:
     def lookup(self, toks, extra) -> int:
         return self.full.lookup(toks, extra)
 
-    def acquire(self, seq_id, toks, extra) -> int:
+    def acquire(self, seq_id, toks, extra, max_tokens: int = -1) -> int:
+        """``max_tokens`` >= 0 caps the cached prefix taken, as in the native manager (0: none)."""
         hit = self.full.lookup(toks, extra)
+        if max_tokens >= 0:
+            hit = min(hit, max_tokens)
         hit = self.swa.acquire_window(seq_id, toks, extra, hit, self.window)
         got = self.full.acquire(seq_id, toks, extra, hit)
         assert got == hit, (got, hit)

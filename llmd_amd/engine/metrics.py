@@ -77,6 +77,10 @@ class EngineMetrics:
                                      registry=r)
         self.spec_accepted_pos = Counter("vllm:spec_decode_num_accepted_tokens_per_pos",
                                          "Accepted tokens per draft position", L + ["position"], registry=r)
+        # prompt scoring (prompt_logprobs / echo): zero until a request asks for it
+        self.scored_tokens = Counter("llmd:prompt_tokens_scored", "Prompt tokens scored (prompt_logprobs / echo)",
+                                     L, registry=r)
+        self._last_scored = 0
         self._last_spec = (0, 0, 0, [])
         self._last_prefix = (0, 0)
         self._last_preempt = 0
@@ -162,6 +166,12 @@ class EngineMetrics:
                 self.spec_accepted_pos.labels(m, str(j)).inc(v - old)
         self._last_spec = (spec.num_drafts, spec.num_draft_tokens, spec.num_accepted_tokens,
                            list(spec.accepted_per_pos))
+
+    def on_scored(self, total: int):
+        """ModelRunner.num_scored (cumulative) -> llmd:prompt_tokens_scored_total."""
+        if total > self._last_scored:
+            self.scored_tokens.labels(self.model).inc(total - self._last_scored)
+            self._last_scored = total
 
     def on_finish(self, r):
         m = self.model

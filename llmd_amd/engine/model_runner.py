@@ -204,6 +204,12 @@ class ModelRunner:
         # compiled grammars (created with the first guided request)
         self.token_table = None
         self.guided_arena = None
+        # prompt scoring: this step's (request, first scored position, rows) and host results; the
+        # prompt tokens scored so far (llmd:prompt_tokens_scored_total)
+        self._score_who = None
+        self._score_host = None
+        self.num_scored = 0
+        self.scored_seen = False
         self.kv = None
         self.num_blocks = 0
         # hybrid KV cache: windowed layers in their own pool (engine/hybrid_kv.py)
@@ -594,6 +600,8 @@ class ModelRunner:
                 tp_broadcast_plan(pl)  # TP followers run the same plan (engine/tp_worker.py)
         with markers.range("llmd.forward"):
             logits = self.run_plan(pl)
+        if pl.get("score") is not None:
+            self._apply_scores()
         if not reqs:
             return DeferredSample.empty() if defer else {}
         if pl.get("embed") and getattr(self, "_last_hidden", None) is not None:
@@ -643,10 +651,84 @@ class ModelRunner:
         mm = self._mm_rows(so)
         if mm is not None:
             pl["mm"] = mm
+        self._score_who = None
+        if self.scored_seen:  # set with the engine's first scored request: no other engine looks
+            sc = self._score_plan(so)
+            if sc is not None:
+                pl["score"] = sc
+                pl["graph"] = False  # a one-token chunk in the middle of a scored prompt is a decode row
         if any(r.params.embed for r in reqs):
             pl["embed"] = True
             pl["graph"] = False
         return pl, reqs
+
+    # ------------------------------------------------------------ prompt scoring
+    @staticmethod
+    def score_rows(sr: ScheduledReq) -> int:
+        """Scoring rows of a prefill chunk [s, e) of a scored request whose prompt has P tokens: rows
+        s .. min(e, P-1)-1, against tokens s+1 .. min(e, P-1). The row that samples is not one of
+        them (its token's logprob is the output logprob). 0 once the request has output tokens: a
+        recompute after its scores were delivered."""
+        r = sr.req
+        if not r.params.scored or r.output_token_ids:
+            return 0
+        return max(min(sr.start + sr.num_new_tokens, r.num_prompt_tokens - 1) - sr.start, 0)
+
+    def _score_plan(self, so: SchedulerOutput):
+        """(row indices, target tokens, alternatives per row) of this step's scoring rows, or None.
+        Who they belong to stays on the runner (``_score_who``), off the plan."""
+        rows, targets, n, who = [], [], [], []
+
+        def add(sr, row0):
+            k = self.score_rows(sr)
+            if k:
+                r = sr.req
+                rows.extend(range(row0, row0 + k))
+                targets.extend(r.prompt_token_ids[sr.start + 1:sr.start + 1 + k])
+                n.extend([r.params.prompt_logprobs] * k)
+                who.append((r, sr.start + 1, k))
+
+        for i, sr in enumerate(so.decodes):  # a chunk the token budget cut to one token
+            if sr.req.params.scored:
+                add(sr, i)
+        row0 = len(so.decodes) + so.num_verify_tokens
+        for sr in so.prefills:
+            if sr.req.params.scored:
+                add(sr, row0)
+            row0 += sr.num_new_tokens
+        if not rows:
+            return None
+        self._score_who = who
+        return rows, targets, n
+
+    def _score(self, h, score):
+        """The scoring rows of the hidden states ``h`` through the LM head and ops.prompt_logprobs,
+        LLMD_SCORE_ROWS rows at a time (256: about 66 MB of bf16 logits at a 128k vocabulary, so
+        the KV pool's profile needs no room for them), copied to the host: the raw model
+        log-softmax, before temperature, penalties, bias, grammar or top-k / top-p."""
+        rows, targets, n = score
+        dev = self.device
+        idx = torch.tensor(rows, dtype=torch.long).to(dev, non_blocking=True)
+        tg = torch.tensor(targets, dtype=torch.int32).to(dev, non_blocking=True)
+        nn = torch.tensor(n, dtype=torch.int32).to(dev, non_blocking=True)
+        step = max(1, int(os.environ.get("LLMD_SCORE_ROWS", "256")))
+        outs = []
+        for a in range(0, len(rows), step):
+            logits = self.model.compute_logits(h.index_select(0, idx[a:a + step]))
+            outs.append(ops.prompt_logprobs(logits, tg[a:a + step], nn[a:a + step]))
+        return tuple(torch.cat(o).cpu().tolist() for o in zip(*outs))
+
+    def _apply_scores(self):
+        """Write the step's scores into their requests, by prompt position."""
+        lp, rank, ids, tlp = self._score_host
+        j = 0
+        for r, pos0, k in self._score_who:
+            m = r.params.prompt_logprobs
+            for i in range(pos0, pos0 + k):
+                r.prompt_logprobs[i] = (lp[j], rank[j], [(t, l) for t, l in zip(ids[j][:m], tlp[j][:m]) if t >= 0])
+                j += 1
+        self.num_scored += j
+        self._score_host = self._score_who = None
 
     def _mm_rows(self, so: SchedulerOutput):
         """Image-placeholder rows of this step's prefill chunks + their embeddings."""
@@ -684,6 +766,8 @@ class ModelRunner:
         if pl["graph"]:
             return self._run_decode_graph(pl)
         h = self._run_eager(pl)
+        if pl.get("score") is not None:
+            self._score_host = self._score(h, pl["score"])
         if not rows:
             return None
         idx = torch.tensor(rows, dtype=torch.long).to(self.device, non_blocking=True)

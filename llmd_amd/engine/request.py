@@ -29,10 +29,17 @@ class SamplingParams:
     logit_bias: Optional[dict] = None  # token id -> additive bias
     top_logprobs: int = 0              # OpenAI: the N most likely alternatives of every output token (<= 20)
     guided: Any = None                 # structured outputs: a compiled llmd_amd.guided.Grammar, or None
+    # prompt scoring (vLLM): the log-probability and rank of every prompt token plus its N most likely
+    # alternatives (<= 20; 0 = the prompt token only); None = the prompt is not scored
+    prompt_logprobs: Optional[int] = None
 
     @property
     def constrained(self) -> bool:
         return self.guided is not None
+
+    @property
+    def scored(self) -> bool:
+        return self.prompt_logprobs is not None
 
     @property
     def penalized(self) -> bool:
@@ -65,9 +72,26 @@ class SamplingParams:
             lp = 1
         elif lp is not None and not isinstance(lp, bool):
             top = lp
+        # prompt scoring: `prompt_logprobs: N`, or the completions form `echo: true` + `logprobs: N`
+        plp = body.get("prompt_logprobs")
+        if plp is not None and (isinstance(plp, bool) or not isinstance(plp, int)):
+            raise ValueError(f"prompt_logprobs must be an integer, got {plp!r}")
+        echo = body.get("echo")
+        if echo is not None and not isinstance(echo, bool):
+            raise ValueError(f"echo must be a boolean, got {echo!r}")
+        if echo and "messages" in body:
+            raise ValueError("echo is not supported on /v1/chat/completions")
+        if plp is not None and body.get("stream"):
+            raise ValueError("prompt_logprobs is not supported with stream")  # as vLLM; echo streams
+        if echo and plp is None and lp:
+            # echo + logprobs: N scores the prompt with N alternatives; echo alone computes nothing
+            plp = 0 if isinstance(lp, bool) else lp
+        if echo and mt is not None and not isinstance(mt, bool) and mt == 0:
+            mt = 1  # echo with max_tokens 0: the server drops the one token the engine generates
         from llmd_amd import guided as _guided
 
         sp = cls(
+            prompt_logprobs=plp,
             guided=_guided.from_request(body),
             max_tokens=int(mt) if mt is not None else default_max,
             temperature=float(body.get("temperature", 1.0) if body.get("temperature") is not None else 1.0),
@@ -101,6 +125,9 @@ class SamplingParams:
             raise ValueError(f"min_p must be in [0, 1], got {self.min_p}")
         if not 0 <= self.top_logprobs <= 20:
             raise ValueError(f"top_logprobs must be in [0, 20], got {self.top_logprobs}")
+        plp = self.prompt_logprobs
+        if plp is not None and (isinstance(plp, bool) or not isinstance(plp, int) or not 0 <= plp <= 20):
+            raise ValueError(f"prompt_logprobs must be an integer in [0, 20], got {plp!r}")
         if self.constrained and self.ignore_eos:
             raise ValueError("ignore_eos cannot be combined with a guided-decoding constraint: "
                              "the grammar decides when EOS is legal")
@@ -189,6 +216,14 @@ class Request:
     guided_state: int = 1
     # output tokens the last step appended (speculative decoding: 1 + the accepted drafts)
     step_new_tokens: int = 1
+    # prompt scoring (params.scored): one entry per prompt token, written by position (a recompute
+    # after a preemption overwrites). Entry 0 is None; entry i is (logprob, rank, [(token id,
+    # logprob), ...]) of prompt token i given the tokens before it
+    prompt_logprobs: Optional[list] = None
+
+    def __post_init__(self):
+        if self.params.scored and self.prompt_logprobs is None:
+            self.prompt_logprobs = [None] * len(self.prompt_token_ids)
 
     @property
     def cache_extra(self) -> int:
@@ -250,3 +285,5 @@ class RequestOutput:
     ttft: Optional[float] = None
     metrics: Optional[dict] = None
     new_top_logprobs: Optional[list] = None  # per new token, for requests with top_logprobs > 0
+    # Request.prompt_logprobs of a scored request, once: with the output that carries its first token
+    prompt_logprobs: Optional[list] = None

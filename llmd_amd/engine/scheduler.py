@@ -342,19 +342,23 @@ class Scheduler:
                 continue
             if not self.bm.has_seq(r.seq_id):
                 toks = self._tokens(r)
-                cached = self.bm.acquire(r.seq_id, toks, r.cache_extra)
+                # a scored request computes every prompt position: it takes references on no cached
+                # block (max_tokens = 0) and reloads nothing from the offload tiers. The blocks it
+                # computes are committed under the usual hashes, so nobody else's hits change
+                scored = r.params.scored
+                cached = (self.bm.acquire(r.seq_id, toks, r.cache_extra, 0) if scored
+                          else self.bm.acquire(r.seq_id, toks, r.cache_extra))
                 r.num_computed_tokens = cached
                 if r.num_preemptions == 0:
                     r.num_cached_tokens = cached
-                if (self.offload is not None and self.cfg.cache.enable_prefix_caching and self.running
-                        and self._reload_cannot_fit(r, cached, budget)):
+                reload = self.offload is not None and self.cfg.cache.enable_prefix_caching and not scored
+                if reload and self.running and self._reload_cannot_fit(r, cached, budget):
                     # it would have to give the reloaded blocks back at once (below) and
                     # reload them again next step: wait holding nothing until blocks free up
                     self.bm.free(r.seq_id)
                     r.num_computed_tokens = 0
                     break
-                if (self.offload is not None and self.cfg.cache.enable_prefix_caching
-                        and self.offload.start_load(r, toks, cached, self.bm)):
+                if reload and self.offload.start_load(r, toks, cached, self.bm):
                     # host / disk blocks continue the prefix: they load asynchronously
                     # (side stream, native read pool) while the engine keeps stepping
                     self.waiting.pop()

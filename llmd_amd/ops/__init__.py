@@ -1075,6 +1075,30 @@ def top_logprobs(logits, n_per_row):
     return ids, lp
 
 
+def prompt_logprobs(logits, targets, n_per_row):
+    """Prompt scoring (logprobs.hip prompt_logprobs_kernel): row ``r`` against its target token
+    ``targets[r]``. Returns ``(lp f32 [R], rank int32 [R], top_ids int32 [R, MAX_TOP_LOGPROBS],
+    top_lp f32 [R, MAX_TOP_LOGPROBS])``: the target's log-softmax over the whole row (no
+    temperature), its vLLM rank - the number of entries ``>=`` the target's, so 1 is the best and
+    ties count - and what ``top_logprobs`` returns for the row and ``n_per_row[r]``. A target
+    outside ``[0, V)`` gives ``-inf / 0`` (nothing is read for it), a ``-inf`` target ``-inf / V``.
+    ``targets`` / ``n_per_row``: int32 ``[R]`` on the logits' device."""
+    R = logits.shape[0]
+    if logits.dim() != 2 or tuple(targets.shape) != (R,) or tuple(n_per_row.shape) != (R,):
+        raise ValueError("prompt_logprobs: logits [R, V], targets [R] and n_per_row [R]")
+    if not _gpu(logits):
+        return ref.prompt_logprobs(logits, targets, n_per_row)
+    C = native()
+    assert C.top_logprobs_max() == MAX_TOP_LOGPROBS
+    dev = logits.device
+    lp = torch.empty(R, dtype=torch.float32, device=dev)
+    rank = torch.empty(R, dtype=torch.int32, device=dev)
+    ids = torch.empty(R, MAX_TOP_LOGPROBS, dtype=torch.int32, device=dev)
+    top_lp = torch.empty(R, MAX_TOP_LOGPROBS, dtype=torch.float32, device=dev)
+    C.prompt_logprobs(logits, targets, n_per_row, lp, rank, ids, top_lp)
+    return lp, rank, ids, top_lp
+
+
 def guided_mask(logits, trans, accept, dfa_off, dfa_n, state, tok_bytes, tok_off, eos_ids):
     """Structured outputs: -inf, in place, over every token that the row's grammar forbids.
 

@@ -193,6 +193,24 @@ def top_logprobs(logits, n_per_row):
     return ids, lp
 
 
+def prompt_logprobs(logits, targets, n_per_row):
+    """Row r against its target token: (log-softmax of the target in fp32, its rank = the number
+    of entries >= the target's stored value, and top_logprobs of the row). A target outside
+    [0, V) gives -inf / 0, a -inf target -inf / V."""
+    lf = logits.float()
+    V = lf.shape[1]
+    t = targets.to(lf.device).long()
+    ok = (t >= 0) & (t < V)
+    tc = t.clamp(0, V - 1)[:, None]
+    xt = lf.gather(-1, tc)
+    lp = torch.log_softmax(lf, -1).gather(-1, tc).squeeze(-1)
+    neg = torch.full_like(lp, float("-inf"))
+    lp = torch.where(ok & (xt.squeeze(-1) > float("-inf")), lp, neg)
+    rank = torch.where(ok, (lf >= xt).sum(-1), torch.zeros_like(t)).to(torch.int32)
+    ids, top_lp = top_logprobs(logits, n_per_row)
+    return lp, rank, ids, top_lp
+
+
 def topk_topp_mask(logits, topk=None, topp=None, temps=None):
     """In-place top-k then top-p (vLLM order): the top-p mass is taken over the top-k
     survivors, renormalised. Ties with the threshold value are kept."""

@@ -292,6 +292,32 @@ class OpenAIServer:
         return {"content": [dict(ent(t, lp), top_logprobs=[ent(a, alp) for a, alp in alts or []])
                             for t, lp, alts in zip(toks, lps, tops)]}
 
+    # ------------------------------------------------------------ prompt scoring
+    def _prompt_logprobs(self, ids, plp) -> list:
+        """vLLM's ``prompt_logprobs`` of a choice: per prompt token ``null`` (the first) or
+        {"<token id>": {"logprob", "rank", "decoded_token"}}, the prompt's own token first, then the
+        alternatives in order (rank = place in the list), the prompt token not repeated."""
+        out: list = [None]
+        for tok, ent in zip(ids[1:], plp[1:]):
+            lp, rank, alts = ent
+            d = {str(tok): {"logprob": lp, "rank": rank, "decoded_token": self.tok.decode([tok])}}
+            for k, (t, l) in enumerate(alts):
+                if t != tok:
+                    d[str(t)] = {"logprob": l, "rank": k + 1, "decoded_token": self.tok.decode([t])}
+            out.append(d)
+        return out
+
+    def _echo_logprobs(self, ids, plp, toks, lps, tops, want_top: bool) -> dict:
+        """/v1/completions ``logprobs`` with ``echo``: the prompt tokens, then ``toks``. The first
+        prompt token has no context: its ``token_logprobs`` / ``top_logprobs`` entries are null.
+        A prompt position lists its own token beside its alternatives, as a generated one does."""
+        p_lps = [None] + [e[0] for e in plp[1:]]
+        p_tops = [None] + [[(t, e[0])] + [a for a in e[2] if a[0] != t] for t, e in zip(ids[1:], plp[1:])]
+        out = self._completion_logprobs(list(ids) + list(toks), p_lps + list(lps), p_tops + list(tops), want_top)
+        if want_top:
+            out["top_logprobs"][0] = None
+        return out
+
     # ------------------------------------------------------------ completions
     async def _guided_prepare(self, body) -> None:
         """Structured outputs (guided_choice / guided_regex / guided_json / structured_outputs /
@@ -367,6 +393,17 @@ class OpenAIServer:
             if chat:
                 params.max_tokens = min(params.max_tokens, self.cfg.sched.max_model_len - len(p))
         ktp = body.get("kv_transfer_params")
+        # echo (/v1/completions): the prompt precedes the completion in text and logprobs; with
+        # max_tokens 0 the engine still generates one token, which is dropped here
+        echo = bool(body.get("echo")) and not chat
+        mt = body.get("max_completion_tokens", body.get("max_tokens"))
+        drop_gen = echo and mt is not None and not isinstance(mt, bool) and mt == 0
+        want_plp = body.get("prompt_logprobs") is not None
+        if params.scored:
+            try:
+                self.aeng.engine.check_scored(params, ktp, mm)
+            except ValueError as e:
+                return _err(400, str(e))
         prio = self._priority(req, body)
         lora = self._lora_id(body)
         rid_base = req.headers.get("x-request-id") or f"{'chatcmpl' if chat else 'cmpl'}-{uuid.uuid4().hex}"
@@ -382,14 +419,20 @@ class OpenAIServer:
             if len(prompts) > 1:
                 return _err(400, "streaming supports a single prompt")
             return await self._stream(req, rids, prompts[0], [pj for _, pj in jobs], prio, ktp, lora, chat,
-                                      include_usage, created, model_name, mm, tools_on, rid_base)
+                                      include_usage, created, model_name, mm, tools_on, rid_base,
+                                      echo=echo, drop_gen=drop_gen)
+        scores: dict = {}  # prompt index -> Request.prompt_logprobs of its sample 0
 
         async def one(k, ids, pk):
             text_ids, lps, tops, last = [], [], [], None
             async for o in self.aeng.generate(rids[k], ids, pk, prio, ktp, lora, mm):
-                text_ids.extend(o.new_token_ids)
-                lps.extend(o.new_logprobs)
-                tops.extend(self._new_tops(o))
+                plp = getattr(o, "prompt_logprobs", None)
+                if plp is not None:
+                    scores[k // params.n] = plp
+                if not drop_gen:
+                    text_ids.extend(o.new_token_ids)
+                    lps.extend(o.new_logprobs)
+                    tops.extend(self._new_tops(o))
                 last = o
                 text = self.tok.decode(text_ids)
                 if pk.stop and any(s in text for s in pk.stop):
@@ -431,9 +474,15 @@ class OpenAIServer:
                 if params.logprobs:  # not requested: no key, as before (a client reads it as null)
                     ch["logprobs"] = self._chat_logprobs(toks, lps, tops)
             else:
-                ch["text"] = text
-                if params.logprobs:
+                ch["text"] = (self.tok.decode(ids) + text) if echo else text
+                plp = scores.get(i // params.n)
+                if params.logprobs and echo and plp is not None:
+                    ch["logprobs"] = self._echo_logprobs(ids, plp, toks, lps, tops, params.top_logprobs > 0)
+                elif params.logprobs:
                     ch["logprobs"] = self._completion_logprobs(toks, lps, tops, params.top_logprobs > 0)
+            if want_plp:
+                plp = scores.get(i // params.n)
+                ch["prompt_logprobs"] = self._prompt_logprobs(ids, plp) if plp is not None else None
             if body.get("return_token_ids"):
                 ch["token_ids"] = toks
             choices.append(ch)
@@ -453,10 +502,13 @@ class OpenAIServer:
             return params
         import dataclasses
 
-        return dataclasses.replace(params, seed=(params.seed + j) if params.seed is not None else None)
+        # only sample 0 scores the prompt (its result serves the prompt's other choices, which keep
+        # their prefix-cache hits)
+        return dataclasses.replace(params, seed=(params.seed + j) if params.seed is not None else None,
+                                   prompt_logprobs=params.prompt_logprobs if j == 0 else None)
 
     async def _stream(self, req, rids, ids, plist, prio, ktp, lora, chat, include_usage, created, model_name,
-                      mm=None, tools_on=False, rid=None):
+                      mm=None, tools_on=False, rid=None, echo=False, drop_gen=False):
         """SSE stream of one prompt's ``n`` choices (chunks of different choices
         interleave, each tagged with its ``index``)."""
         rid = rid or rids[0]
@@ -465,6 +517,10 @@ class OpenAIServer:
         obj = "chat.completion.chunk" if chat else "text_completion"
         wlock = asyncio.Lock()
         n_outs = [0] * len(rids)
+        # echo: every choice's first chunk starts with the prompt; choice 0 scores it for all of them
+        echo_text = self.tok.decode(ids) if echo else ""
+        scored = echo and plist[0].scored
+        plp_fut = asyncio.get_running_loop().create_future() if scored else None
 
         async def send(d):
             async with wlock:
@@ -485,11 +541,15 @@ class OpenAIServer:
                 await send(chunk(idx, {"delta": {"role": "assistant", "content": ""}}, None))
             st = self.parser.streamer(tools_on) if (chat and self.parser is not None) else None
             every = max(1, int(self.opts.stream_interval))
+            first = True  # echo: the next chunk is this choice's first
             async for o in self.aeng.generate(crid, ids, params, prio, ktp, lora, mm):
-                toks.extend(o.new_token_ids)
-                if params.logprobs:
-                    lps.extend(o.new_logprobs)
-                    tops.extend(self._new_tops(o))
+                if plp_fut is not None and not plp_fut.done() and getattr(o, "prompt_logprobs", None) is not None:
+                    plp_fut.set_result(o.prompt_logprobs)
+                if not drop_gen:
+                    toks.extend(o.new_token_ids)
+                    if params.logprobs:
+                        lps.extend(o.new_logprobs)
+                        tops.extend(self._new_tops(o))
                 n_outs[idx] = len(toks)
                 if not o.finished and len(toks) - n_emitted < every:  # --stream-interval
                     continue
@@ -499,9 +559,15 @@ class OpenAIServer:
                     if chat:
                         lp_obj = self._chat_logprobs(toks[new], lps[new], tops[new])
                     else:
-                        lp_obj = self._completion_logprobs(toks[new], lps[new], tops[new],
-                                                           params.top_logprobs > 0, n_chars)
+                        plp = await plp_fut if (first and scored) else None
+                        if plp is not None:  # echo: the first chunk's logprobs begin with the prompt tokens
+                            lp_obj = self._echo_logprobs(ids, plp, toks[new], lps[new], tops[new],
+                                                         params.top_logprobs > 0)
+                        else:
+                            lp_obj = self._completion_logprobs(toks[new], lps[new], tops[new],
+                                                               params.top_logprobs > 0, n_chars)
                         n_chars += sum(len(k) for k in lp_obj["tokens"])
+                first = False
                 n_emitted = len(toks)
                 text = self.tok.decode(toks)
                 stop_hit = False
@@ -510,6 +576,7 @@ class OpenAIServer:
                         k = text.find(s)
                         if k >= 0:
                             text, stop_hit = text[:k], True
+                text = echo_text + text
                 delta = text[len(sent):] if text.startswith(sent) else text
                 sent = text
                 finish = "stop" if stop_hit else (o.finish_reason if o.finished else None)
@@ -540,13 +607,19 @@ class OpenAIServer:
                     self.aeng.abort(crid)
                     break
 
+        def no_scores():  # choice 0 failed before its scores came: the others must not wait for them
+            if plp_fut is not None and not plp_fut.done():
+                plp_fut.set_result(None)
+
         try:
             await asyncio.gather(*[one_choice(i, crid, p) for i, (crid, p) in enumerate(zip(rids, plist))])
         except (ConnectionResetError, asyncio.CancelledError):
+            no_scores()
             for crid in rids:
                 self.aeng.abort(crid)
             raise
         except Exception as e:  # noqa: BLE001
+            no_scores()
             for crid in rids:
                 self.aeng.abort(crid)
             await send({"error": {"message": str(e), "type": type(e).__name__}})
